@@ -11,12 +11,25 @@ are restarted in their slot, so every step does exactly games x sims-per-step si
 Multi-GPU: one process per GPU (torchrun, or `--gpus N` spawns the N ranks itself), games
 sharded (different seeds), no collective on the path; barrier + max-over-ranks timing only.
 
-Extra JSON fields: roofline (the fused tower kernel vs the f32 MFMA peak, HIP events on the
-engine stream over the timed region), bf16_mode (the same window with the bf16 tower, labelled,
-with its stated tolerance), tree_walk (select kernel, algorithmic bytes / time vs HBM peak),
-c2_steady (configs[1] in steady state: 256 games, 6x64 f32, with its tower roofline),
-games_per_hr_measured (C2's games played to the end), cpu_baseline (the oracle, rank 0, N=1,
-bounded sample), training (the C5 gradient step, per-rank and sharded-batch modes).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: set up,
+warm up, time the N steps, write `--dump-outputs DIR` if asked, print the JSON line.  Its extra
+fields come from the timed window itself: roofline (the fused tower kernel vs the f32 MFMA peak,
+HIP events on the engine stream over the timed region) and tree_walk (select kernel, algorithmic
+bytes / time vs HBM peak).
+
+`--full` adds the legs that take runs of their own: bf16_mode (the same window with the bf16 tower,
+labelled, with its stated tolerance), c2_steady (configs[1] in steady state: 256 games, 6x64 f32,
+with its tower roofline), with_fen_cache (`--cache N`), games_per_hr_measured (C2's games played to
+the end), cpu_baseline (the oracle, rank 0, N=1, bounded sample), training (the C5 gradient step,
+per-rank and sharded-batch modes), and, where the engine steps with the persistent per-game kernel,
+the profile pass after the window that the roofline / tree_walk events come from.
+
+`--dump-outputs DIR` writes what a caller of the timed path holds after its last timed step -- the
+roots of the games (improved policy, visit counts, subtree depth: BatchedSearch.read_roots) and the
+engine's counters over the window -- as DIR/<name>.npy (f32 / f64; a fixed sample of the games when
+all of them would pass 64 MB).  When the last timed step completes a move (the default, move-aligned
+window), those roots are the new, unvisited ones of the positions the games have reached, and
+root_moves holds their legal moves.  Seeds and inputs are fixed by the arguments.
 `--rehearse` runs the multi-rank plumbing with a CPU stub engine (no GPU; CI only).
 """
 import argparse
@@ -40,6 +53,8 @@ PMC_SUMMARY = {"f32": os.path.join(ROOT, "profiles", "r06_pmc_tower32w_summary.j
                "bf16": os.path.join(ROOT, "profiles", "r04_pmc_tower_bf16_summary.json")}
 # simulation steps of the instrumented profile pass after the timed window (8 sampled tower launches)
 PROFILE_SIMS = 256
+# --dump-outputs: at most this many games' roots (3 arrays of [n, 4096] f32 = 48 MiB at 1024)
+DUMP_MAX_GAMES = 1024
 # mean plies of complete self-play games of this config (tools/game_length.py: 256 games, 20x256
 # random-init seed 42, 800 sims/move, noise + temperature moves, played to the end)
 # (f32 Winograd net, the headline's; the round-1 file used the bf16 net and is only a fallback)
@@ -326,6 +341,31 @@ def auto_sims_per_step(S, steps, warmup):
     return 100 if S % 100 == 0 else S
 
 
+def dump_outputs(path, rank, sp, counters):
+    """--dump-outputs: the roots of the games after the last timed step (what BatchedSearch.read_roots
+    hands a caller: improved policy, visit counts, subtree depth) and the window's counters, as
+    <path>/<name>.npy (rank 0) or <path>/<name>_rank<r>.npy.  With more than DUMP_MAX_GAMES games, a
+    fixed seeded sample of them (root_games holds their indices).  root_moves is 1 at the move
+    indices a root that has no visits yet holds an edge for, i.e. the legal moves of the position a
+    step that completed a move has just re-rooted to (k_readout's improved reads 0 / 0 there; it is
+    stored as 0)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if rank == 0 else "_rank%d" % rank
+    out = {"counters": np.asarray(counters, np.float64)}
+    if hasattr(sp.search, "read_roots"):
+        imp, vis, dep = sp.search.read_roots()
+        G = imp.shape[0]
+        pick = np.arange(G) if G <= DUMP_MAX_GAMES else \
+            np.sort(np.random.default_rng(0).choice(G, DUMP_MAX_GAMES, replace=False))
+        imp = imp[pick]
+        out.update(root_games=pick.astype(np.float64), root_improved=np.nan_to_num(imp, nan=0.0).astype(np.float32),
+                   root_moves=np.isnan(imp).astype(np.float32), root_visits=vis[pick].astype(np.float32),
+                   root_depth=dep[pick].astype(np.float32))
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + sfx + ".npy"), arr)
+
+
 def play_games_leg(A, device, seed, world, barrier, synchronize, games=256, sims=800, blocks=6, filters=64):
     """C2 (BASELINE.json configs[1]: 256 games x 800 sims/move, 6x64 f32 net) from startpos until
     every game has ended (run_all_episodes, training.rs:340-378): completed games / wall time of
@@ -449,6 +489,12 @@ def main():
     ap.add_argument("--filters", type=int, default=256)
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
                     help="headline precision (the reference computes in f32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline (bf16_mode, c2_steady, with_fen_cache, "
+                         "games_per_hr_measured, training, cpu_baseline, the persistent kernel's profile pass); "
+                         "their options below only matter with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the games' roots and the window's counters as DIR/<name>.npy")
     ap.add_argument("--c2-steps", type=int, default=20,
                     help="moves (800 sims each) of the C2 steady-state leg: 256 games x 6x64 f32 (0 = skip)")
     ap.add_argument("--bf16-steps", type=int, default=-1,
@@ -527,11 +573,11 @@ def main():
         dist_barrier(world)
         synchronize()
 
-    def phase(net, cache, steps, timing, G=G, S=S, K=K, warmup=None):
+    def phase(net, cache, steps, timing, G=G, S=S, K=K, warmup=None, dump=None):
         """Self-play from startpos: warmup steps, then `steps` timed steps of K simulation steps; with
         `timing`, every 32nd simulation step carries HIP events (roofline / tree_walk), in the window
-        or in a profile pass after it (persistent kernel).  G / S / K: the workload (default the
-        headline's)."""
+        or (--full) in a profile pass after it (persistent kernel).  G / S / K: the workload (default
+        the headline's).  `dump`: directory for dump_outputs after the last timed step."""
         warmup = args.warmup if warmup is None else warmup
         if args.rehearse:
             sp = RehearsalSelfPlay(G, S, sh["seed"])
@@ -570,7 +616,9 @@ def main():
             _, vis, dep = sp.search.read_roots()
             digests = [None] * world
             dist.all_gather_object(digests, hashlib.sha1(vis.tobytes() + dep.tobytes()).hexdigest()[:16])
-        prof = min(PROFILE_SIMS, S) if timing and not inwin else 0
+        if dump:
+            dump_outputs(dump, rank, sp, [st1[k] - st0[k] for k in sorted(st0)] + [finished])
+        prof = min(PROFILE_SIMS, S) if timing and not inwin and args.full else 0
         if prof:
             sp.search.timing(reset=True, enable=True)
             sp.run_sims(prof)
@@ -644,9 +692,10 @@ def main():
     legs = {}
     tl = time.perf_counter()
     net = make_net(args.dtype)
-    elapsed, tot, tm, sims_rank = phase(net, 0, args.steps, True)
+    elapsed, tot, tm, sims_rank = phase(net, 0, args.steps, True, dump=args.dump_outputs)
     legs["headline (incl. warmup, profile pass)"] = time.perf_counter() - tl
-    roof = roofline(tm, args.dtype, net)
+    # a plain run with the persistent kernel has no event-bracketed launches (no profile pass)
+    roof = roofline(tm, args.dtype, net) if tm["conv_launches"] or args.rehearse else None
     del net
     sims_all, evals_all, term_all = tot["sims"], tot["evals"], tot["terminal"]
     fin_all, moves_all, depth_all = tot["finished"], tot["moves"], tot["depth"]
@@ -654,7 +703,7 @@ def main():
     # the bf16 throughput mode beside it (labelled; not the headline)
     bf16_res = None
     bf16_steps = args.steps if args.bf16_steps < 0 else args.bf16_steps
-    if args.dtype == "f32" and bf16_steps > 0:
+    if args.full and args.dtype == "f32" and bf16_steps > 0:
         tl = time.perf_counter()
         net16 = make_net("bf16")
         e16, t16, tm16, _ = phase(net16, 0, bf16_steps, True)
@@ -671,7 +720,7 @@ def main():
     # the persistent per-game kernel (one game per CU), its tower timed in a profile pass after
     # the window; beside games_per_hr_measured, which plays C2's games to the end
     c2_res = None
-    if args.c2_steps > 0 and args.dtype == "f32":
+    if args.full and args.c2_steps > 0 and args.dtype == "f32":
         tl = time.perf_counter()
         net2 = None if args.rehearse else A.AlphaZero(6, 64, dtype="f32", device=local, seed=42)
         e2, t2, tm2, _ = phase(net2, 0, args.c2_steps, True, G=256, S=800, K=800, warmup=2)
@@ -686,7 +735,7 @@ def main():
 
     # the reference's FEN cache (tree.rs:214-219) on the same window, on request
     cache_res = None
-    if args.cache > 0:
+    if args.full and args.cache > 0:
         netc = make_net(args.dtype)
         e2, t2, _, _ = phase(netc, args.cache, args.steps, False)
         cache_res = {"value": t2["sims"] / e2, "unit": "sims/s", "evals_per_sim": t2["evals"] / max(t2["sims"], 1),
@@ -695,13 +744,13 @@ def main():
 
     # measured games/hr: C2's configuration played to the end on every rank (training.rs:294-378)
     games_leg = None
-    if args.games_leg and not args.rehearse:
+    if args.full and args.games_leg and not args.rehearse:
         tl = time.perf_counter()
         games_leg = play_games_leg(A, local, sh["seed"], world, barrier, synchronize)
         legs["games_per_hr_measured (C2 played to the end)"] = time.perf_counter() - tl
 
     training = None
-    if args.train_steps > 0 and not args.rehearse and not args.same_device:
+    if args.full and args.train_steps > 0 and not args.rehearse and not args.same_device:
         tl = time.perf_counter()
         training = train_phase(args, A, rank, world, local)
         legs["training"] = time.perf_counter() - tl
@@ -728,6 +777,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -768,9 +818,10 @@ def main():
         "sim_step_ms": {k: tm[k + "_ms"] / max(tm["sim_steps"], 1)
                         for k in ("select", "expand", "encode", "tower", "heads", "backup")},
         "sim_kernels": ("k_sims32w<%d> for every simulation step of the window: one workgroup per game runs its backup, "
-                        "select, expand and network evaluation with no grid-wide step boundary; the roofline / "
-                        "tree_walk events come from a %d-step profile pass after the timed window, whose every-32nd "
-                        "steps run as separate kernels" % (args.filters, tm["profile_sim_steps"])
+                        "select, expand and network evaluation with no grid-wide step boundary; " % args.filters +
+                        ("the roofline / tree_walk events come from a %d-step profile pass after the timed window, "
+                         "whose every-32nd steps run as separate kernels" % tm["profile_sim_steps"] if args.full else
+                         "no roofline / tree_walk events in a plain run (--full adds the profile pass they come from)")
                         ) if tm.get("persistent") else
                        "k_step (backup + select + expand) + the fused tower, two launches per simulation step",
         "evals_per_sim": evals_all / max(sims_all, 1),
@@ -810,7 +861,7 @@ def main():
         roof["wall_bound_note"] = ("executed MFMA FLOPs of every tower launch of the timed window / the window's wall "
                                    "time (k_step, move completions and host work included): a strict lower bound "
                                    "on the tower's rate")
-    if world == 1 and not args.no_cpu_baseline and not args.rehearse:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.rehearse:
         tl = time.perf_counter()
         out["cpu_baseline"] = cpu_baseline(args.blocks, args.filters, args.cpu_threads, args.cpu_games,
                                            args.cpu_sims)

@@ -98,6 +98,31 @@ def test_bench_eight_ranks_c4_layout():
     assert abs(sims - 8 * G * K * steps) < 1e-6 * sims
 
 
+def test_bench_plain_run_is_lean_and_full_adds_the_legs(tmp_path):
+    """A plain run times the headline only (every other leg null, no leg wall time but the
+    headline's); --full runs the legs beside it.  --dump-outputs writes the window's counters
+    (the stub engine has no roots), identical from run to run."""
+    import numpy as np
+    G, K, steps = 16, 8, 3
+    base = ["--gpus", "1", "--rehearse", "--steps", str(steps), "--warmup", "1", "--games", str(G), "--sims", "16",
+            "--sims-per-step", str(K), "--c2-steps", "2"]
+    dumps = []
+    for d in ("a", "b"):
+        rc, lines, err = _bench(base + ["--dump-outputs", str(tmp_path / d)])
+        assert rc == 0 and len(lines) == 1, err[-2000:]
+        dumps.append(np.load(tmp_path / d / "counters.npy"))
+    r = lines[0]
+    assert r["full"] is False and r["steps"] == steps and r["ms_per_step"] > 0
+    assert r["bf16_mode"] is None and r["c2_steady"] is None and r["training"] is None and r["cpu_baseline"] is None
+    assert list(r["legs_wall_s"]) == ["headline (incl. warmup, profile pass)"]
+    assert dumps[0].dtype == np.float64 and np.array_equal(dumps[0], dumps[1]) and G * K * steps in dumps[0]
+    rc, lines, err = _bench(base + ["--full"])
+    assert rc == 0 and len(lines) == 1, err[-2000:]
+    f = lines[0]
+    assert f["full"] is True and f["bf16_mode"]["steps"] == steps and f["c2_steady"]["steps"] == 2
+    assert {"bf16_mode", "c2_steady"} <= set(f["legs_wall_s"])
+
+
 def test_bench_rejects_world_mismatch():
     rc, lines, err = _bench(["--gpus", "1", "--rehearse", "--steps", "1"], env={"WORLD_SIZE": "2", "RANK": "0"})
     assert rc != 0 and not lines and "WORLD_SIZE=2" in err
