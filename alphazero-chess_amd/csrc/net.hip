@@ -475,6 +475,73 @@ std::vector<float> winograd_f32(const std::vector<float>& wf, int F) {
     return o;
 }
 
+// x rounded to the nearest f16 (ties to even, subnormals kept): its bits, and its value in *r.
+// |x| stays below the f16 range here (the Sw rule of winograd_split16)
+uint16_t f16_rne(double x, double* r) {
+    if (!std::isfinite(x)) {
+        *r = x;
+        return std::isnan(x) ? 0x7e00 : (std::signbit(x) ? 0xfc00 : 0x7c00);
+    }
+    const double ax = fabs(x);
+    int e;
+    (void)frexp(ax, &e);                                           // ax in [2^(e-1), 2^e)
+    int q = ax < ldexp(1.0, -14) ? -24 : e - 11;                   // the quantum 2^q
+    double n = nearbyint(ldexp(ax, -q));                           // <= 2048, exact scaling
+    if (n == 2048.0) { n = 1024.0; q++; }
+    *r = copysign(ldexp(n, q), x);
+    const uint16_t sign = std::signbit(x) ? 0x8000 : 0;
+    if (n == 0.0) return sign;
+    if (q + 25 >= 31) { *r = copysign(INFINITY, x); return sign | 0x7c00; }
+    if (n < 1024.0) return sign | (uint16_t)n;                     // subnormal (q = -24)
+    return sign | (uint16_t)(((q + 25) << 10) | ((int)n - 1024));
+}
+
+// The Winograd weights U = G g G^T (f64) for split-f16 products (wino.h wino_core_h16): scaled by
+// Sw, the largest power of two (at most 2^24) with Sw max|U| <= 32768, and split from the f64 value
+// into hi = f16(Sw U), lo = f16(Sw U - hi).  A-fragments of v_mfma_f32_16x16x32_f16:
+// [ci/32][xi][co/16][hi, lo][lane][8], lane = co%16 + 16*((ci%32)/8), component ci%8 -- the same 4
+// bytes per weight as winograd_f32 -- then PF = 2 zero steps.  *unscale = 1 / (Sa Sw), exact.
+std::vector<uint16_t> winograd_split16(const std::vector<float>& wf, int F, float* unscale) {
+    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    const int CF = F / 16, NSTEP = (F / 32) * 16;
+    std::vector<double> U((size_t)F * F * 16);
+    double umax = 0.0;
+    for (size_t cc = 0; cc < (size_t)F * F; cc++) {
+        const float* g = &wf[cc * 9];
+        double gg[4][3];
+        for (int a = 0; a < 4; a++)
+            for (int j = 0; j < 3; j++) gg[a][j] = G[a][0] * g[0 * 3 + j] + G[a][1] * g[1 * 3 + j] + G[a][2] * g[2 * 3 + j];
+        for (int a = 0; a < 4; a++)
+            for (int b = 0; b < 4; b++) {
+                const double u = gg[a][0] * G[b][0] + gg[a][1] * G[b][1] + gg[a][2] * G[b][2];
+                U[cc * 16 + a * 4 + b] = u;
+                if (fabs(u) > umax) umax = fabs(u);
+            }
+    }
+    int se = 24;
+    if (umax > 0.0 && std::isfinite(umax)) {
+        int e;
+        (void)frexp(umax, &e);                                     // umax < 2^e
+        se = 15 - e < 24 ? 15 - e : 24;
+    }
+    *unscale = (float)ldexp(1.0 / (double)WINO16_SA, -se);
+    std::vector<uint16_t> o((size_t)(NSTEP + 2) * CF * 2 * 64 * 8, 0);
+    for (int co = 0; co < F; co++)
+        for (int ci = 0; ci < F; ci++)
+            for (int x = 0; x < 16; x++) {
+                const double s = ldexp(U[((size_t)co * F + ci) * 16 + x], se);
+                double hv, lv;
+                const uint16_t hi = f16_rne(s, &hv);
+                const uint16_t lo = f16_rne(s - hv, &lv);
+                const int step = (ci / 32) * 16 + x;
+                const int lane = (co % 16) + 16 * ((ci % 32) / 8);
+                const size_t at = ((((size_t)step * CF + co / 16) * 2) * 64 + lane) * 8 + ci % 8;
+                o[at] = hi;
+                o[at + 64 * 8] = lo;
+            }
+    return o;
+}
+
 }  // namespace
 
 int net_create(const az_net_desc* d, const float* wts, size_t n, int device, NetDev** out) {
@@ -488,6 +555,7 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
     net->blocks = B; net->filters = F; net->dtype = d->dtype; net->device = device;
     if (const char* e = getenv("AZ_FUSED_TOWER")) net->fused = atoi(e) != 0;
     if (const char* e = getenv("AZ_WINOGRAD")) net->winograd = atoi(e) != 0;
+    if (const char* e = getenv("AZ_WINO_SPLIT16")) net->split16 = atoi(e) != 0;
     AZ_HIP(hipStreamCreateWithFlags(&net->stream, hipStreamNonBlocking));
     const float* p = wts;
     auto fold_conv = [&](int cin, const float* w, const float* bias, const float* bn) {
@@ -521,13 +589,26 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
             if (hipMemcpy(net->in_pk32, u.data(), u.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
             net->in_pk32_bytes = u.size() * 4;
         }
-        if (d->dtype == AZ_DTYPE_F32 && F >= 64 && cin == F) {   // Winograd F(2x2,3x3) copy for tower32w_kernel
+        // residual convs of tower32w_kernel: the split-f16 copy where that path will run (F = 256), the
+        // f32 Winograd copy otherwise -- never both (4 MB per conv)
+        const bool h16 = d->dtype == AZ_DTYPE_F32 && F == 256 && cin == F && net->winograd && net->split16;
+        if (d->dtype == AZ_DTYPE_F32 && F >= 64 && cin == F && !h16) {   // Winograd F(2x2,3x3) copy
             auto u = winograd_f32(wf, F);
             void* du = nullptr;
             if (hipMalloc(&du, u.size() * 4) != hipSuccess) return -1;
             if (hipMemcpy(du, u.data(), u.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
             net->wino_w.push_back(du);
             net->wino_bytes.push_back(u.size() * 4);
+        }
+        if (h16) {
+            float us = 1.0f;
+            auto u = winograd_split16(wf, F, &us);
+            void* du = nullptr;
+            if (hipMalloc(&du, u.size() * 2) != hipSuccess) return -1;
+            if (hipMemcpy(du, u.data(), u.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -1;
+            net->wino16_w.push_back(du);
+            net->wino16_bytes.push_back(u.size() * 2);
+            net->wino16_us.push_back(us);
         }
         if (hipMalloc(&db, F * 4) != hipSuccess) return -1;
         if (hipMemcpy(db, bf.data(), F * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
@@ -621,6 +702,7 @@ void net_destroy(NetDev* n) {
     (void)hipSetDevice(n->device);
     for (void* w : n->conv_w) (void)hipFree(w);
     for (void* w : n->wino_w) (void)hipFree(w);
+    for (void* w : n->wino16_w) (void)hipFree(w);
     for (float* b : n->conv_b) (void)hipFree(b);
     (void)hipFree(n->head);
     (void)hipFree(n->head_frag);

@@ -39,6 +39,7 @@ struct TowerArgs {
     unsigned wbytes[1 + 2 * 40];   // allocation bytes of each w[i] (buffer-load range check)
     const uint4* ww[2 * 40];       // f32 Winograd weights of the residual convs (F = 256, tower32w_kernel)
     unsigned wwbytes[2 * 40];
+    float wus[2 * 40];             // split-f16 products: each conv's unscale 1 / (Sa Sw) (ww = the f16 hi / lo weights)
     const uint4* w0pk;             // the input conv packed for tower32w_kernel (net.hip swizzle_f32_input_packed)
     unsigned w0pk_bytes;
     int blocks;
@@ -245,7 +246,17 @@ template <int NB, int NT, int NPART = 1> struct HeadsScratch {
     static constexpr int FLOATS = STAT + NB * (2 * NW + 4);
 };
 
-template <int F, int RS, int NB, int NT, bool SEARCH, bool F32X = false>
+// ReLU; KEEP: a NaN stays NaN (fmaxf returns its other operand).  The split-f16 tower marks an
+// activation beyond the f16 range with NaN (wino.h WinoXf::split16), and that NaN has to reach
+// the policy and the value
+template <bool KEEP> __device__ __forceinline__ float relu_nan(float v) {
+    if constexpr (KEEP) return v < 0.0f ? 0.0f : v;
+    else return fmaxf(v, 0.0f);
+}
+
+// NANKEEP: the two ReLUs keep NaN; the softmax and tanh behind them then give NaN (a NaN logit is
+// skipped by the max and makes the exp sum NaN)
+template <int F, int RS, int NB, int NT, bool SEARCH, bool F32X = false, bool NANKEEP = false>
 __device__ __forceinline__ void heads_group(const char* __restrict__ xb, float* __restrict__ scr, int b0, int nb,
                                             int row0, int tid, const uint4* __restrict__ hfrag,
                                             const float* __restrict__ head, float* pol_out, float* val_out,
@@ -384,7 +395,7 @@ __device__ __forceinline__ void heads_group(const char* __restrict__ xb, float* 
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int ch = cf * 16 + 4 * h + r;
-                if (ch < 40) p1v1[bb * PV + ch * P1S + sq] = fmaxf(acc[cf][r] + b40v[cf][r], 0.0f);
+                if (ch < 40) p1v1[bb * PV + ch * P1S + sq] = relu_nan<NANKEEP>(acc[cf][r] + b40v[cf][r]);
             }
     }
     wino_stamp(tr, 1901);
@@ -462,7 +473,7 @@ __device__ __forceinline__ void heads_group(const char* __restrict__ xb, float* 
         const int bb = w;
         float hs = l1bv;
         for (int i = 0; i < NW * NPART; i++) hs += red[(bb * NW * NPART + i) * 64 + lane];
-        float hv = t_wave_sum(fmaxf(hs, 0.0f) * l2wv);
+        float hv = t_wave_sum(relu_nan<NANKEEP>(hs) * l2wv);
         if (lane == 0) stat[bb * (2 * NW + 4) + 2 * NW] = tanhf(hv + l2bv);
     }
     if constexpr (SEARCH) {                             // thread 0 reserves eval-log slots
@@ -953,11 +964,11 @@ __device__ __forceinline__ unsigned long long* tt_slot(int w) {
 __device__ __forceinline__ unsigned long long* tt_slot(int) { return nullptr; }
 #endif
 
-template <int F, bool RESID>
+template <int F, bool RESID, bool H16>
 __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
                                           const __amdgpu_buffer_rsrc_t rW, const __amdgpu_buffer_rsrc_t rN,
-                                          const float* __restrict__ bias,
-                                          f32x4 (&wr)[WinoCfg<F>::PF][WinoCfg<F>::XS][WinoCfg<F>::NN],
+                                          const float* __restrict__ bias, float unscale,
+                                          f32x4 (&wr)[WinoCfg<F>::PF][WinoRing<F, H16>::RX][WinoCfg<F>::NN],
                                           f32x4 (&xres)[WinoCfg<F>::NN][4], int w, int lane, bool pre_in,
                                           bool pre_out, int vsel, int* flag, int seq,
                                           unsigned long long* tr = nullptr) {
@@ -977,7 +988,8 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
     f32x4 y[NN][4];
     wino_stamp(tr, 0);
     // F = 64: the single chunk's V alternates between two buffers from conv to conv (vsel)
-    wino_core<F>(ldsb, vbase + (F == 64 ? vsel * VBYTES : 0), rW, rN, bias, wr, w, lane, y, pre_in, tr);
+    if constexpr (H16) wino_core_h16<F>(ldsb, vbase, rW, rN, bias, unscale, wr, w, lane, y, pre_in, tr);
+    else wino_core<F>(ldsb, vbase + (F == 64 ? vsel * VBYTES : 0), rW, rN, bias, wr, w, lane, y, pre_in, tr);
     wino_stamp(tr, 10);
     f32x4 o[NN][4];
 #pragma unroll
@@ -986,8 +998,9 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
         for (int q = 0; q < 4; q++) {
             f32x4 v = y[n][q];
             if constexpr (RESID) v += xres[n][q];
+            // split-f16: an activation beyond the f16 range arrives as NaN and stays NaN (fmaxf drops it)
 #pragma unroll
-            for (int r = 0; r < 4; r++) v[r] = fmaxf(v[r], 0.0f);
+            for (int r = 0; r < 4; r++) v[r] = relu_nan<H16>(v[r]);
             *reinterpret_cast<f32x4*>(ldsb + out_addr(n, q >> 1, q & 1)) = v;
             o[n][q] = v;
         }
@@ -1003,7 +1016,7 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
             else
                 while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seq)
                     __builtin_amdgcn_s_sleep(1);
-            WinoXf<F>(ldsb, vbase, w, lane).both(0, 0);
+            WinoXf<F>(ldsb, vbase, w, lane).template both<H16>(0, 0);
         }
     } else if constexpr (F == 64) {
         // F = 64: each wave's 16 output channels are a quarter of the next conv's single chunk;
@@ -1019,11 +1032,12 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
 }
 
 // one board (batch row row0) through the Winograd f32 tower, all NWV waves of the workgroup
-template <int F, bool SEARCH>
+template <int F, bool SEARCH, bool H16>
 __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes, const TowerArgs& ta, int row0,
                                                       float* __restrict__ pol_out, float* __restrict__ val_out,
                                                       const SearchOut& so, int tid) {
-    constexpr int NWV = WinoCfg<F>::NWV, NT = NWV * 64, NN = WinoCfg<F>::NN, XS = WinoCfg<F>::XS;
+    static_assert(!H16 || F == 256, "split-f16 products: F = 256 only");
+    constexpr int NWV = WinoCfg<F>::NWV, NT = NWV * 64, NN = WinoCfg<F>::NN, XS = WinoRing<F, H16>::RX;
     constexpr int RSF = F / 4 + 2, RSI = 32 / 4 + 2;
     constexpr int XSZ = 64 * RSF;                        // ACT, uint4 slots
     // both V buffers (one when a single chunk covers the input), also planes staging / heads scratch
@@ -1074,15 +1088,18 @@ __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes,
     f32x4 wring[PF][XS][NN];
     if (ta.blocks > 0) {
         const __amdgpu_buffer_rsrc_t r = t32_rsrc(ta.ww[0], ta.wwbytes[0]);
-        const int voff = wino_voff<F>(w, lane);
+        const int voff = H16 ? wino16_voff<F>(w, lane) : wino_voff<F>(w, lane);
 #pragma unroll
         for (int i = 0; i < PF; i++)
 #pragma unroll
             for (int xs = 0; xs < XS; xs++)
 #pragma unroll
-                for (int n = 0; n < NN; n++)
-                    wring[i][xs][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                                    r, voff + n * 1024 + wino_toff<F>(0, i * XS + xs), 0, 0));
+                for (int n = 0; n < NN; n++) {
+                    // split-f16: xs = the hi / lo plane of step i (wino_core_h16)
+                    const int off = H16 ? (2 * n + xs) * 1024 + i * (F / 16) * 2048
+                                        : n * 1024 + wino_toff<F>(0, i * XS + xs);
+                    wring[i][xs][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff + off, 0, 0));
+                }
     }
     for (int b = 0; b < ta.blocks; b++) {
         const unsigned wb3 = b + 1 < ta.blocks ? ta.wwbytes[2 * b + 2] : 0u;   // after the last conv: nothing (reads 0)
@@ -1092,23 +1109,23 @@ __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes,
         // F = 256 / 64: each conv transforms the next conv's chunk 0 at its end (conv_wino; C3 A/B
         // -0.3 % against the tail transform alone)
         constexpr bool PRE = F == 256 || F == 64;
-        conv_wino<F, false>(ldsb, vbase, r1, r2, ta.b[1 + 2 * b], wring, xres, w, lane, PRE && b > 0, PRE, 0, flag,
+        conv_wino<F, false, H16>(ldsb, vbase, r1, r2, ta.b[1 + 2 * b], ta.wus[2 * b], wring, xres, w, lane, PRE && b > 0, PRE, 0, flag,
                             2 * b + 1, tr ? tr + 3 + 64 * b : nullptr);
-        conv_wino<F, true>(ldsb, vbase, r2, r3, ta.b[2 + 2 * b], wring, xres, w, lane, PRE, PRE && b + 1 < ta.blocks,
+        conv_wino<F, true, H16>(ldsb, vbase, r2, r3, ta.b[2 + 2 * b], ta.wus[2 * b + 1], wring, xres, w, lane, PRE, PRE && b + 1 < ta.blocks,
                            F == 64 ? 1 : 0, flag, 2 * b + 2, tr ? tr + 35 + 64 * b : nullptr);
     }
-    heads_group<F, RSF, 1, NT, SEARCH, true>(ldsb, reinterpret_cast<float*>(V), 0, 1, row0, tid, ta.head_frag32, ta.head,
+    heads_group<F, RSF, 1, NT, SEARCH, true, H16>(ldsb, reinterpret_cast<float*>(V), 0, 1, row0, tid, ta.head_frag32, ta.head,
                                              pol_out, val_out, so, tr);
     wino_stamp(tr, 3 + 64 * 20);
 }
 
-template <int F, bool SEARCH>
+template <int F, bool SEARCH, bool H16>
 __global__ void __launch_bounds__(WinoCfg<F>::NWV * 64)
 tower32w_kernel(const float* __restrict__ planes, TowerArgs ta, const int* __restrict__ count_ptr, int rows,
                 float* __restrict__ pol_out, float* __restrict__ val_out, SearchOut so) {
     const int count = count_ptr ? min(load_fresh(count_ptr), rows) : rows;
     if ((int)blockIdx.x >= count) return;
-    tower32w_board<F, SEARCH>(planes, ta, blockIdx.x, pol_out, val_out, so, threadIdx.x);
+    tower32w_board<F, SEARCH, H16>(planes, ta, blockIdx.x, pol_out, val_out, so, threadIdx.x);
 }
 
 // k_sims32w: simulation steps [step0, step1) of one game per workgroup, with no grid-wide step
@@ -1128,7 +1145,7 @@ template <int F> struct SimsCfg<F, true> {
     static_assert(TowerCfg<F>::BPB == 1, "persistent bf16 kernel: one board per workgroup");
     static constexpr int NT = (F / (16 * TowerCfg<F>::NCO)) * TowerCfg<F>::WB * 64;
 };
-template <int F, bool BF16>
+template <int F, bool BF16, bool H16 = false>
 __global__ void __launch_bounds__((SimsCfg<F, BF16>::NT))
 k_sims32w(Engine E, TowerArgs ta, SearchOut so, int step0, int step1) {
     __shared__ int s_kind;
@@ -1176,7 +1193,7 @@ k_sims32w(Engine E, TowerArgs ta, SearchOut so, int step0, int step1) {
         wino_stamp(tr, 1914);
         if (kind == X_ROW) {
             if constexpr (BF16) tower_board<F, true>(nullptr, ta, g, 1, nullptr, nullptr, so, tid);
-            else tower32w_board<F, true>(nullptr, ta, g, nullptr, nullptr, so, tid);
+            else tower32w_board<F, true, H16>(nullptr, ta, g, nullptr, nullptr, so, tid);
         }
         __syncthreads();
         wino_stamp(tr, 1915);
@@ -1188,10 +1205,17 @@ bool tower_supported(const NetDev* n) {
            (n->filters == 256 || n->filters == 128 || n->filters == 64 || n->filters == 32);
 }
 
-bool wino_supported(const NetDev* n) {
-    return n->dtype == AZ_DTYPE_F32 && n->winograd && n->filters >= 64 && (int)n->wino_w.size() == 2 * n->blocks &&
-           n->in_pk32 != nullptr;
+// the residual convs' split-f16 weights were built (net_create then builds no f32 Winograd copy)
+static bool wino16_built(const NetDev* n) {
+    return n->split16 && n->filters == 256 && (int)n->wino16_w.size() == 2 * n->blocks;
 }
+
+bool wino_supported(const NetDev* n) {
+    return n->dtype == AZ_DTYPE_F32 && n->winograd && n->filters >= 64 && n->in_pk32 != nullptr &&
+           ((int)n->wino_w.size() == 2 * n->blocks || wino16_built(n));
+}
+
+bool wino_split16(const NetDev* n) { return wino_supported(n) && wino16_built(n); }
 
 static TowerArgs tower_args(const NetDev* n) {
     TowerArgs ta;
@@ -1204,9 +1228,11 @@ static TowerArgs tower_args(const NetDev* n) {
     ta.head = n->head;
     ta.head_frag = reinterpret_cast<const uint4*>(n->head_frag);
     ta.head_frag32 = reinterpret_cast<const uint4*>(n->head_frag32);
-    for (size_t i = 0; i < n->wino_w.size(); i++) {
-        ta.ww[i] = reinterpret_cast<const uint4*>(n->wino_w[i]);
-        ta.wwbytes[i] = (unsigned)n->wino_bytes[i];
+    const bool h16 = wino_split16(n);
+    for (size_t i = 0; i < (h16 ? n->wino16_w.size() : n->wino_w.size()); i++) {
+        ta.ww[i] = reinterpret_cast<const uint4*>(h16 ? n->wino16_w[i] : n->wino_w[i]);
+        ta.wwbytes[i] = (unsigned)(h16 ? n->wino16_bytes[i] : n->wino_bytes[i]);
+        ta.wus[i] = h16 ? n->wino16_us[i] : 1.0f;
     }
     ta.w0pk = reinterpret_cast<const uint4*>(n->in_pk32);
     ta.w0pk_bytes = (unsigned)n->in_pk32_bytes;
@@ -1232,6 +1258,10 @@ int sims_persistent(const NetDev* n, const Engine& E, const SearchOut& so, int s
     if (n->filters == FF) {                                                                            \
         k_sims32w<FF, false><<<E.G, SimsCfg<FF, false>::NT, 0, st>>>(E, ta, so, step0, step1);          \
         return hipGetLastError() == hipSuccess ? 0 : fail("persistent simulation kernel launch failed"); \
+    }
+    if (wino_split16(n)) {
+        k_sims32w<256, false, true><<<E.G, SimsCfg<256, false>::NT, 0, st>>>(E, ta, so, step0, step1);
+        return hipGetLastError() == hipSuccess ? 0 : fail("persistent simulation kernel launch failed");
     }
     AZ_SIMS32W(256) AZ_SIMS32W(128) AZ_SIMS32W(64)
 #undef AZ_SIMS32W
@@ -1266,15 +1296,18 @@ int tower_forward(NetDev* n, const void* planes, const int* count, int rows, flo
         return hipGetLastError() == hipSuccess ? 0 : fail("f32 tower launch failed");                          \
     }
     if (n->dtype == AZ_DTYPE_F32) {
-#define AZ_TOWER32W(FF)                                                                                       \
+#define AZ_TOWER32W(FF, H16)                                                                                  \
         if (n->filters == FF) {                                                                                \
             constexpr int NT = WinoCfg<FF>::NWV * 64;                                                          \
-            if (so) tower32w_kernel<FF, true><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s); \
-            else tower32w_kernel<FF, false><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s);  \
+            if (so) tower32w_kernel<FF, true, H16><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s); \
+            else tower32w_kernel<FF, false, H16><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s);  \
             return hipGetLastError() == hipSuccess ? 0 : fail("f32 Winograd tower launch failed");             \
         }
+        if (wino_split16(n)) {
+            AZ_TOWER32W(256, true)
+        }
         if (wino_supported(n)) {
-            AZ_TOWER32W(256) AZ_TOWER32W(128) AZ_TOWER32W(64)
+            AZ_TOWER32W(256, false) AZ_TOWER32W(128, false) AZ_TOWER32W(64, false)
         }
 #undef AZ_TOWER32W
         AZ_TOWER32(256) AZ_TOWER32(128) AZ_TOWER32(64) AZ_TOWER32(32)

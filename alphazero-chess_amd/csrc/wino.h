@@ -100,6 +100,9 @@ template <int F> struct WinoCfg;
 template <> struct WinoCfg<256> { static constexpr int NWV = 8, NN = 2, XS = 1, CH = 32, PF = 2; };
 template <> struct WinoCfg<128> { static constexpr int NWV = 8, NN = 1, XS = 2, CH = 32, PF = 2; };
 template <> struct WinoCfg<64> { static constexpr int NWV = 4, NN = 1, XS = 2, CH = 64, PF = 2; };
+// weight ring of the tower: [PF steps][RX][NN] 16-byte fragments; RX = the step's points (f32
+// products) or its hi / lo planes (split-f16 products, one point per step)
+template <int F, bool H16> struct WinoRing { static constexpr int RX = H16 ? 2 : WinoCfg<F>::XS; };
 // Winograd weight fragment offsets: wave w's lane base (output fragments NN w..) and the byte
 // offset of ring step t (16-channel group kl = t / 16, point t % 16) of chunk cg
 template <int F> __device__ __forceinline__ int wino_voff(int w, int lane) {
@@ -108,6 +111,13 @@ template <int F> __device__ __forceinline__ int wino_voff(int w, int lane) {
 template <int F> __device__ __forceinline__ int wino_toff(int cg, int t) {
     constexpr int KPC = WinoCfg<F>::CH / 16, CF = F / 16;
     return ((cg * KPC + t / 16) * 16 + t % 16) * CF * 1024;
+}
+
+// split-f16 weights: wave w's lane base (its 2 NN fragments of a step are consecutive: output
+// fragment n, plane pl at (2 n + pl) KB); step t = chunk t / 16, point t % 16 at t * (F / 16) * 2 KB
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+template <int F> __device__ __forceinline__ int wino16_voff(int w, int lane) {
+    return (2 * WinoCfg<F>::NN * w * 64 + lane) * 16;
 }
 
 // The input transform V[buf] <- B^T d B of one chunk, one (channel, tile) item per thread and
@@ -193,13 +203,67 @@ template <int F> struct WinoXf {
     }
     // the first NWV / 2 waves transform chunk c into V[buf] for all NWV waves (their own items and
     // those of the waves NWV / 2 later): F = 256 only (IT = 1, NWV = 8)
-    __device__ __forceinline__ void both(int c, int buf) const {
+    template <bool H16 = false> __device__ __forceinline__ void both(int c, int buf) const {
         static_assert(IT == 1 && NWV == 8, "two items per thread of the first half");
         Patch d0, d1;
         load(c, d0, 0);
-        load(c, d1, 1);
-        store(buf, d0, 0);
-        store(buf, d1, 1);
+        if constexpr (H16) {   // one item at a time: the deeper weight ring leaves no room for both patches
+            store16(buf, d0, 0);
+            load(c, d1, 1);
+            store16(buf, d1, 1);
+        } else {
+            load(c, d1, 1);
+            store(buf, d0, 0);
+            store(buf, d1, 1);
+        }
+    }
+    // ---- split-f16 V (wino_core_h16): the chunk's V as two f16 planes, hi at 0 and lo at VBYTES / 2,
+    // each [16 xi][channel octet][16 tile slots][8] f16 (1 KB per point: the B fragment of
+    // v_mfma_f32_16x16x32_f16 is one ds_read_b128 per lane, 8 channels of one tile).  The transform
+    // stays f32; each value is then scaled by WINO16_SA and split hi = f16(s), lo = f16(s - hi)
+    // (round to nearest even: 22 significand bits between them).  A lane owns one channel, its
+    // neighbour lane ^ 1 the other channel of the pair: they swap (hi, lo) over DPP, the even lane
+    // writes the pair's hi, the odd lane its lo, one ds_write_b32 each.  Tile slot = tile ^ 2 (octet
+    // & 3) ^ 4 (lo plane): the 32 lanes of a write (16 channels x 2 tiles, a hi and a lo lane per
+    // pair; 32 banks) cover 8 slot values mod 8 x 4 pairs = 32 distinct banks; the B-fragment read
+    // is the f32 layout's (quad -> octet), the XOR by 4 uniform within a read: both conflict-free
+    // (an XOR by 8 left the hi and lo lanes of a pair on one bank: PMC 22 % of LDS cycles conflicts).
+    // A value beyond the f16 range (|V| Sa >= 65520) splits into (inf, -inf): their products sum to
+    // NaN, which every ReLU of the split-f16 tower keeps, the heads' included (tower.hip relu_nan).
+    static __device__ __forceinline__ unsigned split16(float v) {
+        const float s = v * WINO16_SA;
+        const _Float16 hi = (_Float16)s;
+        const _Float16 lo = (_Float16)(s - (float)hi);
+        return (unsigned)__builtin_bit_cast(unsigned short, hi) | ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16);
+    }
+    __device__ __forceinline__ int vwr16(int tch) const {   // + xi * 1024
+        const int odd = lane & 1;
+        return odd * (VBYTES / 2) + (tch >> 3) * 256 +
+               (((4 * tty + ttx) ^ (2 * ((tch >> 3) & 3)) ^ (4 * odd)) * 16) + ((tch & 7) >> 1) * 4;
+    }
+    __device__ __forceinline__ void store16(int buf, const Patch& d, int g = 0) const {
+        static_assert(CH == 32, "two f16 planes of 16 KB per chunk");
+        const int tl = vgpr_index(ttx);
+        const f32x2 m = f32x2{tl > 0 ? 1.0f : 0.0f, tl < 3 ? 1.0f : 0.0f};
+        // v_perm_b32 selectors: even lane (own.hi, other.hi), odd lane (other.lo, own.lo)
+        const unsigned sel = (lane & 1) ? 0x03020706u : 0x05040100u;
+#pragma unroll
+        for (int it = 0; it < IT; it++) {
+            f32x2 v[4][2];   // [column k][row pair]
+            xform(d[it], m, v);
+            char* vb = ldsb + vbase + buf * VBYTES + vwr16(tchan(it, g));
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+#pragma unroll
+                for (int rp = 0; rp < 2; rp++)
+#pragma unroll
+                    for (int e = 0; e < 2; e++) {
+                        const unsigned own = split16(e ? v[k][rp].y : v[k][rp].x);
+                        // quad_perm [1, 0, 3, 2]: the other channel of the pair
+                        const unsigned oth = (unsigned)__builtin_amdgcn_update_dpp(0, (int)own, 0xB1, 0xF, 0xF, true);
+                        *reinterpret_cast<unsigned*>(vb + ((2 * rp + e) * 4 + k) * 1024) = __builtin_amdgcn_perm(oth, own, sel);
+                    }
+        }
     }
 };
 
@@ -222,6 +286,7 @@ constexpr int DPP_SHL = 0x100, DPP_SHR = 0x110;
 AZ_PK2(pkc_nadd, "neg_lo:[1,1] neg_hi:[1,1]")                 // (-a.x - b.x, -a.y - b.y)
 AZ_PK3(pkc_fma_nc, "neg_lo:[0,0,1] neg_hi:[0,0,1]")            // (a.x m.x - c.x, a.y m.y - c.y)
 AZ_PK3(pkc_nfma, "neg_lo:[1,0,0] neg_hi:[1,0,0]")              // (-a.x m.x + c.x, -a.y m.y + c.y)
+AZ_PK3(pkc_fma, "")                                            // (a.x m.x + c.x, a.y m.y + c.y)
 #undef AZ_PK2
 #undef AZ_PK3
 template <int F>
@@ -449,6 +514,141 @@ __device__ __forceinline__ void wino_core(char* __restrict__ ldsb, int vbase,
             const f32x2 q1 = pk_add(pk_sub(pk_sub(s0[1], s0[2]), s0[3]), br);
             const f32x2 q2 = pk_add(pk_add(pk_add(s1[0], s1[1]), s1[2]), br);
             const f32x2 q3 = pk_add(pk_sub(pk_sub(s1[1], s1[2]), s1[3]), br);
+            y[n][0][2 * p] = q0.x; y[n][0][2 * p + 1] = q0.y;
+            y[n][1][2 * p] = q1.x; y[n][1][2 * p + 1] = q1.y;
+            y[n][2][2 * p] = q2.x; y[n][2][2 * p + 1] = q2.y;
+            y[n][3][2 * p] = q3.x; y[n][3][2 * p + 1] = q3.y;
+        }
+    }
+}
+
+// ====================================================================== split-f16 point GEMMs
+// wino_core_h16: wino_core for F = 256 with the 16 point GEMMs on v_mfma_f32_16x16x32_f16 (16 issue
+// cycles for K = 32, against 8 x 32 for the f32 MFMA).  Each f32 factor is scaled by a power of two
+// and split into two f16 (11-bit significands), x = hi + lo to 22 bits, and the product is
+// hi hi + hi lo + lo hi, accumulated in f32: the dropped lo lo term is below 2^-22 relative, less
+// than the rounding of the f32 accumulation (tools/split16_numerics.py).  Same tiling, ACT,
+// accumulator / output layout, residual and epilogue as wino_core (the MFMA C/D layout does not
+// depend on the input type); differences:
+//   V        two f16 planes per chunk (WinoXf::store16), the same 32 KB per 32-channel chunk;
+//   weights  [32-channel chunk][xi][co/16][hi, lo][64 lanes][8] f16 (net.hip winograd_split16), lane
+//            = co % 16 + 16 (ci % 32 / 8), scaled per conv by Sw: the same 4 bytes per weight;
+//   step     one point x 32 channels: 4 weight fragments (2 output fragments x hi, lo), 2 B
+//            fragments, 6 MFMAs; 16 steps per chunk;
+//   unscale  the conv's 1 / (Sa Sw), a power of two (exact), folded into the output transform's
+//            bias add as one packed FMA.
+template <int F>
+__device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase,
+                                              const __amdgpu_buffer_rsrc_t rW, const __amdgpu_buffer_rsrc_t rN,
+                                              const float* __restrict__ bias, float unscale,
+                                              f32x4 (&wr)[WinoCfg<F>::PF][2][WinoCfg<F>::NN], int w, int lane,
+                                              f32x4 (&y)[WinoCfg<F>::NN][4], bool pre = false,
+                                              unsigned long long* tr = nullptr) {
+    static_assert(F == 256, "split-f16 core: 8 waves x 32 output channels");
+    constexpr int CF = F / 16;
+    constexpr int NWV = WinoCfg<F>::NWV, NN = WinoCfg<F>::NN, CH = WinoCfg<F>::CH, PF = WinoCfg<F>::PF;
+    constexpr int VBYTES = CH * 1024, NCHUNK = F / CH, SPC = 16;     // one step per point
+    constexpr int STEPB = CF * 2 * 1024;                             // weight bytes of a step
+    // steps of B fragments read ahead: a step lasts ~700 cycles at the weight stream's rate, one is
+    // enough, and 2 spilled 12 more VGPRs per block (C3 A/B: tower 13.0-13.3 ms against 13.4-13.7)
+    constexpr int LA = 1;
+    static_assert(CH == 32 && SPC % PF == 0 && SPC % LA == 0, "ring slots must be compile-time");
+    const int l16 = lane & 15, h = lane >> 4;
+    const int vrd = h * 256 + ((l16 ^ (2 * h)) * 16);                // hi plane; lo: slot ^ 4, + VBYTES / 2
+    const int vrl = VBYTES / 2 + h * 256 + ((l16 ^ (2 * h) ^ 4) * 16);
+    const WinoXf<F> xf(ldsb, vbase, w, lane);
+    const int co0 = w * 16 * NN + h * 4;
+    f32x4 acc[16][NN];
+#pragma unroll
+    for (int x = 0; x < 16; x++)
+#pragma unroll
+        for (int n = 0; n < NN; n++) {
+            f32x2 z0, z1;
+            asm volatile("v_mov_b64 %0, 0" : "=v"(z0));
+            asm volatile("v_mov_b64 %0, 0" : "=v"(z1));
+            acc[x][n] = f32x4{z0.x, z0.y, z1.x, z1.y};
+        }
+    const int voff = wino16_voff<F>(w, lane);
+    if (!pre) {   // chunk 0 not transformed by the caller
+        typename WinoXf<F>::Patch d0;
+        xf.load(0, d0);
+        xf.store16(0, d0);
+        __syncthreads();
+    }
+    wino_stamp(tr, 1);
+#pragma unroll 1
+    for (int c = 0; c < NCHUNK; c++) {
+        const int vb = vbase + (c & 1) * VBYTES;
+        const bool more = c + 1 < NCHUNK;
+        f16x8 bq[LA][2];
+#pragma unroll
+        for (int i = 0; i < LA; i++) {
+            bq[i][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + i * 1024);
+            bq[i][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + i * 1024);
+        }
+#pragma unroll
+        for (int st = 0; st < SPC; st++) {
+            const f16x8 bh = bq[st % LA][0], bl = bq[st % LA][1];
+            if (st + LA < SPC) {
+                bq[st % LA][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + (st + LA) * 1024);
+                bq[st % LA][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + (st + LA) * 1024);
+            }
+            f16x8 a[2][NN];
+#pragma unroll
+            for (int pl = 0; pl < 2; pl++)
+#pragma unroll
+                for (int n = 0; n < NN; n++) a[pl][n] = __builtin_bit_cast(f16x8, wr[st % PF][pl][n]);
+            {
+                // ring step st + PF; past this conv's last step the refills read the next conv's first
+                const bool nxt = st + PF >= SPC && !more;
+                const int tn = c * SPC + st + PF;
+                const int to = nxt ? tn - NCHUNK * SPC : tn;
+#pragma unroll
+                for (int pl = 0; pl < 2; pl++)
+#pragma unroll
+                    for (int n = 0; n < NN; n++)
+                        wr[st % PF][pl][n] = __builtin_bit_cast(
+                            f32x4, __builtin_amdgcn_raw_buffer_load_b128(nxt ? rN : rW, voff + (2 * n + pl) * 1024,
+                                                                         to * STEPB, 0));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // hi hi, hi lo, lo hi of each output fragment, the two fragments' chains interleaved
+#pragma unroll
+            for (int n = 0; n < NN; n++) acc[st][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][n], bh, acc[st][n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < NN; n++) acc[st][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][n], bl, acc[st][n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < NN; n++) acc[st][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1][n], bh, acc[st][n], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (st == 4) wino_stamp(tr, 20 + c);
+            // the next chunk's transform: as in wino_core, by the first wave of each SIMD pair
+            if (st == SPC - 1 && more && w < NWV / 2) xf.template both<true>(c + 1, (c + 1) & 1);
+        }
+        wino_stamp(tr, 12 + c);
+        if (more) __syncthreads();   // (none after the last chunk: see wino_core)
+        wino_stamp(tr, 2 + c);
+    }
+    // output transform Y = A^T M A per (output fragment n, channel pair), x unscale + bias
+    const f32x2 us = f32x2{unscale, unscale};
+#pragma unroll
+    for (int n = 0; n < NN; n++) {
+        const f32x4 bb = bias ? *reinterpret_cast<const f32x4*>(bias + co0 + n * 16) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int p = 0; p < 2; p++) {
+            f32x2 m[16];
+#pragma unroll
+            for (int x = 0; x < 16; x++) m[x] = p ? f32x2{acc[x][n][2], acc[x][n][3]} : f32x2{acc[x][n][0], acc[x][n][1]};
+            const f32x2 br = p ? f32x2{bb[2], bb[3]} : f32x2{bb[0], bb[1]};
+            f32x2 s0[4], s1[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                s0[j] = pk_add(pk_add(m[j], m[4 + j]), m[8 + j]);
+                s1[j] = pk_sub(pk_sub(m[4 + j], m[8 + j]), m[12 + j]);
+            }
+            const f32x2 q0 = pkc_fma(pk_add(pk_add(s0[0], s0[1]), s0[2]), us, br);
+            const f32x2 q1 = pkc_fma(pk_sub(pk_sub(s0[1], s0[2]), s0[3]), us, br);
+            const f32x2 q2 = pkc_fma(pk_add(pk_add(s1[0], s1[1]), s1[2]), us, br);
+            const f32x2 q3 = pkc_fma(pk_sub(pk_sub(s1[1], s1[2]), s1[3]), us, br);
             y[n][0][2 * p] = q0.x; y[n][0][2 * p + 1] = q0.y;
             y[n][1][2 * p] = q1.x; y[n][1][2 * p + 1] = q1.y;
             y[n][2][2 * p] = q2.x; y[n][2][2 * p + 1] = q2.y;

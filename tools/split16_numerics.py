@@ -1,0 +1,126 @@
+"""Numerics of split-f16 point GEMMs in the Winograd F(2x2,3x3) tower (CPU, numpy), in the setting of
+tools/wino44_numerics.py: a 20x256 residual tower of random-init 3x3 convs over 8x8 boards (4 boards;
+BatchNorm at its random-init identity, ReLU, residual adds) against the same tower in float64 with
+direct convs.  The transforms run in float32.  Split products: V scaled by Sa and U by Sw (powers of
+two), each split hi = f16(s), lo = f16(s - hi) (round to nearest even), M = hi hi + hi lo + lo hi with
+exact f16 x f16 products (exact in f32: 11 + 11 bits) summed in float32 (numpy's blocked sums, not the
+MFMA's order -- the error scale, not the bits), then unscaled by 1 / (Sa Sw).
+Settles: the scale rule (Sa; Sw per conv = the largest power of two with Sw max|U| <= 32768, as
+net.hip winograd_split16), the representable range (|V| <= 4 |x|, so |x| < 65504 / (4 Sa); the input
+scaled up until the error leaves the f32-product level), f16 subnormals kept or flushed, and the split
+source (U from its f64 value or from its rounded f32 value).
+Usage: python tools/split16_numerics.py [filters=256] [blocks=20]   (output: profiles/split16_numerics.txt)"""
+import sys
+
+import numpy as np
+
+rng = np.random.default_rng(0)
+G = np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]])
+BT = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], np.float32)
+AT = np.array([[1, 1, 1, 0], [0, 1, -1, -1]], np.float32)
+F16_MIN_NORMAL = 2.0 ** -14
+
+
+def conv_direct(x, w, dt):   # x [B,8,8,C], w [Co,Ci,3,3]
+    B, H, W, C = x.shape
+    xp = np.zeros((B, H + 2, W + 2, C), dt)
+    xp[:, 1:-1, 1:-1] = x
+    cols = np.stack([xp[:, i:i + H, j:j + W, :] for i in range(3) for j in range(3)], axis=3)
+    wm = w.transpose(2, 3, 1, 0).reshape(9 * C, -1).astype(dt)
+    return (cols.reshape(B * H * W, 9 * C).astype(dt) @ wm).reshape(B, H, W, -1)
+
+
+def split(s, flush):
+    """s (f32 or f64) -> (hi, lo) as float32 holding f16 values"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        hi = s.astype(np.float16)
+        lo = (s - hi.astype(s.dtype)).astype(np.float16)
+    if flush:
+        hi = np.where(np.abs(hi) < F16_MIN_NORMAL, np.float16(0), hi)
+        lo = np.where(np.abs(lo) < F16_MIN_NORMAL, np.float16(0), lo)
+    return hi.astype(np.float32), lo.astype(np.float32)
+
+
+def sw_exp(U):
+    m = np.abs(U).max()
+    return 24 if m == 0 else min(24, 15 - int(np.frexp(m)[1]))
+
+
+class Conv:
+    """one conv's point GEMMs: mode 'f32' (U rounded once to f32), or split-f16 with (Sa, flush, src)"""
+
+    def __init__(self, mode, sa=64.0, flush=False, src="f64", scale=True):
+        self.mode, self.sa, self.flush, self.src, self.scale = mode, np.float32(sa if scale else 1.0), flush, src, scale
+        self.vmax = 0.0
+
+    def __call__(self, x, w):
+        B, H, W, C = x.shape
+        U = np.einsum('ik,ockl,jl->ijoc', G, w.astype(np.float64), G)
+        xp = np.zeros((B, H + 2, W + 2, C), np.float32)
+        xp[:, 1:-1, 1:-1] = x
+        d = np.stack([xp[:, 2 * t:2 * t + 4, 2 * u:2 * u + 4, :] for t in range(4) for u in range(4)], axis=1)  # B,16,4,4,C
+        V = np.einsum('ia,btajc,kj->btikc', BT, d, BT).astype(np.float32)
+        if self.mode == "f32":
+            M = np.einsum('ijoc,btijc->btijo', U.astype(np.float32), V).astype(np.float32)
+        else:
+            se = sw_exp(U) if self.scale else 0
+            Us = np.ldexp(U if self.src == "f64" else U.astype(np.float32), se)
+            uh, ul = split(Us, self.flush)
+            Vs = V * self.sa
+            self.vmax = max(self.vmax, float(np.abs(Vs).max()))
+            vh, vl = split(Vs, self.flush)
+            ein = lambda u, v: np.einsum('ijoc,btijc->btijo', u, v).astype(np.float32)
+            with np.errstate(over="ignore", invalid="ignore"):
+                M = ((ein(uh, vh) + ein(uh, vl)).astype(np.float32) + ein(ul, vh)).astype(np.float32)
+                M = M * np.float32(np.ldexp(1.0 / float(self.sa), -se))
+        Y = np.einsum('ai,btijo,cj->btaco', AT, M, AT).astype(np.float32)    # B,16,2,2,Co
+        return Y.reshape(B, 4, 4, 2, 2, -1).transpose(0, 1, 3, 2, 4, 5).reshape(B, 8, 8, -1)
+
+
+def tower(x, ws, conv, dt):
+    s = dt(1.0 / np.sqrt(1.0 + 1e-5))
+    h, amax = x, float(np.abs(x).max())
+    for b in range(len(ws) // 2):
+        y = np.maximum(conv(h, ws[2 * b]) * s, 0).astype(dt)
+        amax = max(amax, float(np.abs(y).max()))
+        y = (conv(y, ws[2 * b + 1]) * s + h).astype(dt)
+        h = np.maximum(y, 0).astype(dt)
+        with np.errstate(invalid="ignore"):
+            amax = max(amax, float(np.abs(h).max()))
+    return h, amax
+
+
+F = int(sys.argv[1]) if len(sys.argv) > 1 else 256
+NB = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+Bn = 4
+bound = 1.0 / np.sqrt(F * 9)
+ws = [rng.uniform(-bound, bound, (F, F, 3, 3)) for _ in range(2 * NB)]
+x0 = np.maximum(rng.standard_normal((Bn, 8, 8, F)), 0)   # stand-in for the input conv's output
+print("%dx%d tower, %d boards; Sw exponents of the convs: %s" % (NB, F, Bn, sorted({sw_exp(np.einsum('ik,ockl,jl->ijoc', G, w, G)) for w in ws})))
+
+
+def report(name, xs, conv):
+    ref, amax = tower(x0 * xs, ws, lambda h, w: conv_direct(h, w, np.float64), np.float64)
+    out, _ = tower((x0 * xs).astype(np.float32), ws, conv, np.float32)
+    with np.errstate(invalid="ignore"):
+        e = np.abs(out - ref)
+        rms = np.sqrt((e ** 2).mean() / (ref ** 2).mean())
+    extra = "  max |Sa V| %.0f" % conv.vmax if getattr(conv, "vmax", 0) else ""
+    print("%-46s in x%-5g max |act| %7.1f  rms rel %.3e  max abs %.3e%s" % (name, xs, amax, rms, e.max(), extra))
+
+
+print("-- scale rule (input x1)")
+report("F(2x2) f32 products", 1, Conv("f32"))
+report("split-f16, no scaling", 1, Conv("h16", scale=False))
+report("split-f16, no scaling, flushed", 1, Conv("h16", scale=False, flush=True))
+for sa in (16, 64, 256):
+    report("split-f16 Sa=%d" % sa, 1, Conv("h16", sa))
+    report("split-f16 Sa=%d, flushed" % sa, 1, Conv("h16", sa, flush=True))
+print("-- split source (Sa=64)")
+report("split-f16 Sa=64, U split from f32", 1, Conv("h16", 64, src="f32"))
+report("split-f16 Sa=64, U split from f32, flushed", 1, Conv("h16", 64, flush=True, src="f32"))
+print("-- range (Sa=64: |x| < 65504 / 256 = 255.8; the error is relative, f32 products for comparison)")
+for xs in (1 / 32, 8, 32, 64):
+    report("F(2x2) f32 products", xs, Conv("f32"))
+    report("split-f16 Sa=64", xs, Conv("h16", 64))
+    report("split-f16 Sa=64, flushed", xs, Conv("h16", 64, flush=True))
