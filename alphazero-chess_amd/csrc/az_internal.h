@@ -24,6 +24,11 @@ namespace azi {
 // power of two.  |V| <= 4 |x|, so the layer inputs must stay below 65504 / (4 Sa) = 255.8
 // (tools/split16_numerics.py: the scale rule)
 constexpr float WINO16_SA = 64.0f;
+// AZ_WINO_SPLIT16 is a level: 0 no split-f16 products, 1 (the default) at 256 filters, 2 also at 128
+// and 64 filters (measured, not yet the default there: DESIGN.md 5.5)
+static inline bool wino16_selected(int level, int filters) {
+    return filters == 256 ? level >= 1 : (filters == 128 || filters == 64) && level >= 2;
+}
 
 void set_error(const std::string& msg);
 int fail(const std::string& msg);
@@ -145,13 +150,13 @@ struct NetDev {
     std::vector<void*> wino_w;      // f32 F >= 64: Winograd-transformed residual conv weights (tower32w_kernel)
     std::vector<size_t> wino_bytes;
     bool winograd = AZ_WINOGRAD_DEFAULT != 0;   // tower32w_kernel for f32 F >= 64 nets (env AZ_WINOGRAD=0/1)
-    // f32 F = 256: the same weights scaled by Sw (a power of two per conv) and split into f16 hi / lo
-    // A-fragments of v_mfma_f32_16x16x32_f16 (wino.h wino_core_h16), and each conv's 1 / (Sa Sw);
-    // built instead of wino_w (which then stays empty) when split16 is on
+    // f32 nets the split16 level selects (wino16_selected): the same weights scaled by Sw (a power of
+    // two per conv) and split into f16 hi / lo A-fragments of v_mfma_f32_16x16x32_f16 (wino.h
+    // wino_core_h16), and each conv's 1 / (Sa Sw); built instead of wino_w (which then stays empty)
     std::vector<void*> wino16_w;
     std::vector<size_t> wino16_bytes;
     std::vector<float> wino16_us;
-    bool split16 = AZ_WINO_SPLIT16_DEFAULT != 0;   // split-f16 point GEMMs in tower32w_kernel<256> (env AZ_WINO_SPLIT16=0/1)
+    int split16 = AZ_WINO_SPLIT16_DEFAULT;   // split-f16 point GEMMs in tower32w_kernel (env AZ_WINO_SPLIT16=0/1/2)
     float* head = nullptr;          // folded head weights (f32)
     void* head_frag = nullptr;      // 1x1 F->40 head conv as bf16 hi/lo MFMA A-fragments (fused tower)
     void* in_pk32 = nullptr;        // f32 Winograd nets: the input conv's weights with channels 16-18 of 4 taps packed per k-step (tower32w)
@@ -211,7 +216,7 @@ int net_planes_from_host_layout(NetDev* n, const float* d_in, int rows, void* pl
 // fused tower (tower.hip): input conv + residual tower + heads in one launch (bf16 and f32).
 bool tower_supported(const NetDev* n);
 bool wino_supported(const NetDev* n);   // f32, F >= 64, Winograd weights built: tower32w_kernel
-bool wino_split16(const NetDev* n);     // ... with split-f16 MFMA products (F = 256)
+bool wino_split16(const NetDev* n);     // ... with split-f16 MFMA products (wino16_selected)
 // persistent per-game simulation kernel (tower.hip, k_sims32w): simulation steps [step0, step1) of
 // every game, tree steps and Winograd evaluations in one workgroup per game, all backed up at the end
 bool sims_persistent_supported(const NetDev* n);

@@ -500,7 +500,10 @@ uint16_t f16_rne(double x, double* r) {
 // Sw, the largest power of two (at most 2^24) with Sw max|U| <= 32768, and split from the f64 value
 // into hi = f16(Sw U), lo = f16(Sw U - hi).  A-fragments of v_mfma_f32_16x16x32_f16:
 // [ci/32][xi][co/16][hi, lo][lane][8], lane = co%16 + 16*((ci%32)/8), component ci%8 -- the same 4
-// bytes per weight as winograd_f32 -- then PF = 2 zero steps.  *unscale = 1 / (Sa Sw), exact.
+// bytes per weight as winograd_f32 -- then 2 zero steps.  *unscale = 1 / (Sa Sw), exact.  The ring of
+// wino_core_h16 never reads past a conv's last step (its refills switch to the next conv's buffer,
+// whose first 8 steps exist at every F, or to an empty resource after the last conv, which reads 0),
+// and every refill is a buffer load bounded by the allocation's size.
 std::vector<uint16_t> winograd_split16(const std::vector<float>& wf, int F, float* unscale) {
     static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
     const int CF = F / 16, NSTEP = (F / 32) * 16;
@@ -555,7 +558,7 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
     net->blocks = B; net->filters = F; net->dtype = d->dtype; net->device = device;
     if (const char* e = getenv("AZ_FUSED_TOWER")) net->fused = atoi(e) != 0;
     if (const char* e = getenv("AZ_WINOGRAD")) net->winograd = atoi(e) != 0;
-    if (const char* e = getenv("AZ_WINO_SPLIT16")) net->split16 = atoi(e) != 0;
+    if (const char* e = getenv("AZ_WINO_SPLIT16")) net->split16 = atoi(e);
     AZ_HIP(hipStreamCreateWithFlags(&net->stream, hipStreamNonBlocking));
     const float* p = wts;
     auto fold_conv = [&](int cin, const float* w, const float* bias, const float* bn) {
@@ -589,9 +592,10 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
             if (hipMemcpy(net->in_pk32, u.data(), u.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
             net->in_pk32_bytes = u.size() * 4;
         }
-        // residual convs of tower32w_kernel: the split-f16 copy where that path will run (F = 256), the
-        // f32 Winograd copy otherwise -- never both (4 MB per conv)
-        const bool h16 = d->dtype == AZ_DTYPE_F32 && F == 256 && cin == F && net->winograd && net->split16;
+        // residual convs of tower32w_kernel: the split-f16 copy where that path will run (the
+        // AZ_WINO_SPLIT16 level, wino16_selected), the f32 Winograd copy otherwise -- never both (4 MB
+        // per conv at F = 256)
+        const bool h16 = d->dtype == AZ_DTYPE_F32 && cin == F && net->winograd && wino16_selected(net->split16, F);
         if (d->dtype == AZ_DTYPE_F32 && F >= 64 && cin == F && !h16) {   // Winograd F(2x2,3x3) copy
             auto u = winograd_f32(wf, F);
             void* du = nullptr;

@@ -37,7 +37,7 @@ struct TowerArgs {
     const uint4* head_frag;        // 1x1 F->40 head conv as bf16 hi/lo MFMA A-fragments (net.hip)
     const uint4* head_frag32;      // the same conv as f32 A-fragments (f32 tower)
     unsigned wbytes[1 + 2 * 40];   // allocation bytes of each w[i] (buffer-load range check)
-    const uint4* ww[2 * 40];       // f32 Winograd weights of the residual convs (F = 256, tower32w_kernel)
+    const uint4* ww[2 * 40];       // Winograd weights of the residual convs (tower32w_kernel): f32, or split-f16 (wus)
     unsigned wwbytes[2 * 40];
     float wus[2 * 40];             // split-f16 products: each conv's unscale 1 / (Sa Sw) (ww = the f16 hi / lo weights)
     const uint4* w0pk;             // the input conv packed for tower32w_kernel (net.hip swizzle_f32_input_packed)
@@ -968,7 +968,7 @@ template <int F, bool RESID, bool H16>
 __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
                                           const __amdgpu_buffer_rsrc_t rW, const __amdgpu_buffer_rsrc_t rN,
                                           const float* __restrict__ bias, float unscale,
-                                          f32x4 (&wr)[WinoCfg<F>::PF][WinoRing<F, H16>::RX][WinoCfg<F>::NN],
+                                          f32x4 (&wr)[WinoRing<F, H16>::PF][WinoRing<F, H16>::RX][WinoCfg<F>::NN],
                                           f32x4 (&xres)[WinoCfg<F>::NN][4], int w, int lane, bool pre_in,
                                           bool pre_out, int vsel, int* flag, int seq,
                                           unsigned long long* tr = nullptr) {
@@ -988,8 +988,9 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
     f32x4 y[NN][4];
     wino_stamp(tr, 0);
     // F = 64: the single chunk's V alternates between two buffers from conv to conv (vsel)
-    if constexpr (H16) wino_core_h16<F>(ldsb, vbase, rW, rN, bias, unscale, wr, w, lane, y, pre_in, tr);
-    else wino_core<F>(ldsb, vbase + (F == 64 ? vsel * VBYTES : 0), rW, rN, bias, wr, w, lane, y, pre_in, tr);
+    const int vconv = vbase + (F == 64 ? vsel * VBYTES : 0);
+    if constexpr (H16) wino_core_h16<F>(ldsb, vconv, rW, rN, bias, unscale, wr, w, lane, y, pre_in, tr);
+    else wino_core<F>(ldsb, vconv, rW, rN, bias, wr, w, lane, y, pre_in, tr);
     wino_stamp(tr, 10);
     f32x4 o[NN][4];
 #pragma unroll
@@ -1022,7 +1023,7 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
         // F = 64: each wave's 16 output channels are a quarter of the next conv's single chunk;
         // the wave transforms them from its registers (DPP neighbour exchange) into the other V
         // buffer -- no ACT round trip, no barrier between the epilogue and the transform
-        if (pre_out) wino_xform_regs<F>(o[0], ldsb + vbase + (1 - vsel) * VBYTES, w, lane);
+        if (pre_out) wino_xform_regs<F, H16>(o[0], ldsb + vbase + (1 - vsel) * VBYTES, w, lane);
         (void)flag; (void)seq;
     } else {
         (void)pre_out; (void)flag; (void)seq;
@@ -1036,14 +1037,14 @@ template <int F, bool SEARCH, bool H16>
 __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes, const TowerArgs& ta, int row0,
                                                       float* __restrict__ pol_out, float* __restrict__ val_out,
                                                       const SearchOut& so, int tid) {
-    static_assert(!H16 || F == 256, "split-f16 products: F = 256 only");
-    constexpr int NWV = WinoCfg<F>::NWV, NT = NWV * 64, NN = WinoCfg<F>::NN, XS = WinoRing<F, H16>::RX;
+    constexpr int NWV = WinoCfg<F>::NWV, NT = NWV * 64, NN = WinoCfg<F>::NN;
+    constexpr int XS = WinoRing<F, H16>::XS, RX = WinoRing<F, H16>::RX;
     constexpr int RSF = F / 4 + 2, RSI = 32 / 4 + 2;
     constexpr int XSZ = 64 * RSF;                        // ACT, uint4 slots
     // both V buffers (one when a single chunk covers the input), also planes staging / heads scratch
     // (F = 64: two single-chunk buffers, alternating from conv to conv)
     constexpr int VSZ = (F / WinoCfg<F>::CH > 1 || F == 64 ? 2 : 1) * WinoCfg<F>::CH * 1024 / 16;
-    constexpr int PF = WinoCfg<F>::PF;
+    constexpr int PF = WinoRing<F, H16>::PF;
     constexpr int ZN = 16 + F / 4;
     constexpr int PAD = WINO_PAD_SQ * RSF;               // zero squares either side of ACT
     static_assert(HeadsScratch<1, NT, heads_npart(NT, true)>::FLOATS * 4 <= VSZ * 16, "heads scratch must fit in V");
@@ -1085,20 +1086,20 @@ __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes,
     }
     wino_stamp(tr, 2);
     f32x4 xres[NN][4];
-    f32x4 wring[PF][XS][NN];
+    f32x4 wring[PF][RX][NN];
     if (ta.blocks > 0) {
         const __amdgpu_buffer_rsrc_t r = t32_rsrc(ta.ww[0], ta.wwbytes[0]);
         const int voff = H16 ? wino16_voff<F>(w, lane) : wino_voff<F>(w, lane);
 #pragma unroll
         for (int i = 0; i < PF; i++)
 #pragma unroll
-            for (int xs = 0; xs < XS; xs++)
+            for (int rx = 0; rx < RX; rx++)
 #pragma unroll
                 for (int n = 0; n < NN; n++) {
-                    // split-f16: xs = the hi / lo plane of step i (wino_core_h16)
-                    const int off = H16 ? (2 * n + xs) * 1024 + i * (F / 16) * 2048
-                                        : n * 1024 + wino_toff<F>(0, i * XS + xs);
-                    wring[i][xs][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff + off, 0, 0));
+                    // split-f16: rx = point rx / 2 of step i, its hi / lo plane (wino_core_h16)
+                    const int off = H16 ? (2 * n + rx % 2) * 1024 + (i * XS + rx / 2) * (F / 16) * 2048
+                                        : n * 1024 + wino_toff<F>(0, i * XS + rx);
+                    wring[i][rx][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff + off, 0, 0));
                 }
     }
     for (int b = 0; b < ta.blocks; b++) {
@@ -1207,7 +1208,7 @@ bool tower_supported(const NetDev* n) {
 
 // the residual convs' split-f16 weights were built (net_create then builds no f32 Winograd copy)
 static bool wino16_built(const NetDev* n) {
-    return n->split16 && n->filters == 256 && (int)n->wino16_w.size() == 2 * n->blocks;
+    return wino16_selected(n->split16, n->filters) && (int)n->wino16_w.size() == 2 * n->blocks;
 }
 
 bool wino_supported(const NetDev* n) {
@@ -1254,16 +1255,15 @@ int sims_persistent(const NetDev* n, const Engine& E, const SearchOut& so, int s
         k_sims32w<64, true><<<E.G, SimsCfg<64, true>::NT, 0, st>>>(E, ta, so, step0, step1);
         return hipGetLastError() == hipSuccess ? 0 : fail("persistent simulation kernel launch failed");
     }
-#define AZ_SIMS32W(FF)                                                                                  \
+#define AZ_SIMS32W(FF, H16)                                                                             \
     if (n->filters == FF) {                                                                            \
-        k_sims32w<FF, false><<<E.G, SimsCfg<FF, false>::NT, 0, st>>>(E, ta, so, step0, step1);          \
+        k_sims32w<FF, false, H16><<<E.G, SimsCfg<FF, false>::NT, 0, st>>>(E, ta, so, step0, step1);     \
         return hipGetLastError() == hipSuccess ? 0 : fail("persistent simulation kernel launch failed"); \
     }
     if (wino_split16(n)) {
-        k_sims32w<256, false, true><<<E.G, SimsCfg<256, false>::NT, 0, st>>>(E, ta, so, step0, step1);
-        return hipGetLastError() == hipSuccess ? 0 : fail("persistent simulation kernel launch failed");
+        AZ_SIMS32W(256, true) AZ_SIMS32W(128, true) AZ_SIMS32W(64, true)
     }
-    AZ_SIMS32W(256) AZ_SIMS32W(128) AZ_SIMS32W(64)
+    AZ_SIMS32W(256, false) AZ_SIMS32W(128, false) AZ_SIMS32W(64, false)
 #undef AZ_SIMS32W
     return fail("persistent simulation kernel: unsupported filters");
 }
@@ -1304,7 +1304,7 @@ int tower_forward(NetDev* n, const void* planes, const int* count, int rows, flo
             return hipGetLastError() == hipSuccess ? 0 : fail("f32 Winograd tower launch failed");             \
         }
         if (wino_split16(n)) {
-            AZ_TOWER32W(256, true)
+            AZ_TOWER32W(256, true) AZ_TOWER32W(128, true) AZ_TOWER32W(64, true)
         }
         if (wino_supported(n)) {
             AZ_TOWER32W(256, false) AZ_TOWER32W(128, false) AZ_TOWER32W(64, false)

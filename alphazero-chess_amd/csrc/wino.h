@@ -100,9 +100,17 @@ template <int F> struct WinoCfg;
 template <> struct WinoCfg<256> { static constexpr int NWV = 8, NN = 2, XS = 1, CH = 32, PF = 2; };
 template <> struct WinoCfg<128> { static constexpr int NWV = 8, NN = 1, XS = 2, CH = 32, PF = 2; };
 template <> struct WinoCfg<64> { static constexpr int NWV = 4, NN = 1, XS = 2, CH = 64, PF = 2; };
-// weight ring of the tower: [PF steps][RX][NN] 16-byte fragments; RX = the step's points (f32
-// products) or its hi / lo planes (split-f16 products, one point per step)
-template <int F, bool H16> struct WinoRing { static constexpr int RX = H16 ? 2 : WinoCfg<F>::XS; };
+// weight ring of the tower: [PF steps][RX][NN] 16-byte fragments; a ring step covers XS points, RX =
+// those points (f32 products) or their hi / lo planes, [2 xs + plane] (split-f16 products).
+// Split-f16: one point per step where a wave owns two output fragments (F = 256: their two
+// accumulator chains interleave), two points per step where it owns one (F = 128, 64: one point's
+// hi hi, hi lo, lo hi is a single dependent chain).  There a step is 6 MFMAs of 16 cycles, a third of
+// the f32 step, so the ring is 4 steps deep: the same ~400 cycles of MFMA issue ahead of the loads
+template <int F, bool H16> struct WinoRing {
+    static constexpr int XS = H16 ? (WinoCfg<F>::NN == 1 ? 2 : 1) : WinoCfg<F>::XS;
+    static constexpr int RX = H16 ? 2 * XS : XS;
+    static constexpr int PF = H16 && WinoCfg<F>::NN == 1 ? 4 : WinoCfg<F>::PF;
+};
 // Winograd weight fragment offsets: wave w's lane base (output fragments NN w..) and the byte
 // offset of ring step t (16-channel group kl = t / 16, point t % 16) of chunk cg
 template <int F> __device__ __forceinline__ int wino_voff(int w, int lane) {
@@ -218,8 +226,8 @@ template <int F> struct WinoXf {
         }
     }
     // ---- split-f16 V (wino_core_h16): the chunk's V as two f16 planes, hi at 0 and lo at VBYTES / 2,
-    // each [16 xi][channel octet][16 tile slots][8] f16 (1 KB per point: the B fragment of
-    // v_mfma_f32_16x16x32_f16 is one ds_read_b128 per lane, 8 channels of one tile).  The transform
+    // each [16 xi][channel octet][16 tile slots][8] f16 (XST16 = 32 CH bytes per point, 1 KB at CH = 32:
+    // the B fragment of v_mfma_f32_16x16x32_f16 is one ds_read_b128 per lane, 8 channels of one tile).  The transform
     // stays f32; each value is then scaled by WINO16_SA and split hi = f16(s), lo = f16(s - hi)
     // (round to nearest even: 22 significand bits between them).  A lane owns one channel, its
     // neighbour lane ^ 1 the other channel of the pair: they swap (hi, lo) over DPP, the even lane
@@ -236,13 +244,13 @@ template <int F> struct WinoXf {
         const _Float16 lo = (_Float16)(s - (float)hi);
         return (unsigned)__builtin_bit_cast(unsigned short, hi) | ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16);
     }
-    __device__ __forceinline__ int vwr16(int tch) const {   // + xi * 1024
+    static constexpr int XST16 = CH * 32;
+    __device__ __forceinline__ int vwr16(int tch) const {   // + xi * XST16
         const int odd = lane & 1;
         return odd * (VBYTES / 2) + (tch >> 3) * 256 +
                (((4 * tty + ttx) ^ (2 * ((tch >> 3) & 3)) ^ (4 * odd)) * 16) + ((tch & 7) >> 1) * 4;
     }
     __device__ __forceinline__ void store16(int buf, const Patch& d, int g = 0) const {
-        static_assert(CH == 32, "two f16 planes of 16 KB per chunk");
         const int tl = vgpr_index(ttx);
         const f32x2 m = f32x2{tl > 0 ? 1.0f : 0.0f, tl < 3 ? 1.0f : 0.0f};
         // v_perm_b32 selectors: even lane (own.hi, other.hi), odd lane (other.lo, own.lo)
@@ -261,7 +269,7 @@ template <int F> struct WinoXf {
                         const unsigned own = split16(e ? v[k][rp].y : v[k][rp].x);
                         // quad_perm [1, 0, 3, 2]: the other channel of the pair
                         const unsigned oth = (unsigned)__builtin_amdgcn_update_dpp(0, (int)own, 0xB1, 0xF, 0xF, true);
-                        *reinterpret_cast<unsigned*>(vb + ((2 * rp + e) * 4 + k) * 1024) = __builtin_amdgcn_perm(oth, own, sel);
+                        *reinterpret_cast<unsigned*>(vb + ((2 * rp + e) * 4 + k) * XST16) = __builtin_amdgcn_perm(oth, own, sel);
                     }
         }
     }
@@ -283,13 +291,20 @@ constexpr int DPP_SHL = 0x100, DPP_SHR = 0x110;
 // that the transform multiplies by 0 -- exactly WinoXf::load + store on the same outputs in LDS,
 // bit for bit.  Writes the 16 points x 4 channels of the lane's (quad, tile) into V at vdst with
 // one ds_write_b128 per point.
+// H16: V in the split-f16 layout (WinoXf::store16: two f16 planes, [xi][octet][tile slot][8]).  The
+// lane's quad is half h & 1 of octet cq / 2: each value goes through WinoXf::split16, the lane
+// groups h and h ^ 1 exchange (the even one gives its lo and takes the other's hi), and per point
+// the even group writes the octet's hi, the odd group its lo, one ds_write_b128 each -- the bits
+// WinoXf::load + store16 would write.  The 8 lanes a ds_write_b128 services together are 8 tile
+// slots distinct mod 8: 32 distinct banks (one ds_write_b64 per lane and plane instead was 2-way:
+// its 16 lanes cover 16 slots of 8 bytes; PMC + 1.44 M conflict cycles per launch, 16 % of LDS cycles).
 AZ_PK2(pkc_nadd, "neg_lo:[1,1] neg_hi:[1,1]")                 // (-a.x - b.x, -a.y - b.y)
 AZ_PK3(pkc_fma_nc, "neg_lo:[0,0,1] neg_hi:[0,0,1]")            // (a.x m.x - c.x, a.y m.y - c.y)
 AZ_PK3(pkc_nfma, "neg_lo:[1,0,0] neg_hi:[1,0,0]")              // (-a.x m.x + c.x, -a.y m.y + c.y)
 AZ_PK3(pkc_fma, "")                                            // (a.x m.x + c.x, a.y m.y + c.y)
 #undef AZ_PK2
 #undef AZ_PK3
-template <int F>
+template <int F, bool H16 = false>
 __device__ __forceinline__ void wino_xform_regs(const f32x4 (&o)[4], char* __restrict__ vdst, int w, int lane) {
     static_assert(F == 64 && WinoCfg<F>::NN == 1, "one chunk, one output fragment per wave");
     constexpr int XST = WinoCfg<F>::CH * 64;
@@ -351,9 +366,37 @@ __device__ __forceinline__ void wino_xform_regs(const f32x4 (&o)[4], char* __res
                 out[4 * a + b][2 * cp + 1] = V[a][b].y;
             }
     }
-    char* vb = vdst + cq * 256 + ((l16 ^ (2 * (cq & 3))) * 16);
+    if constexpr (H16) {
+        constexpr int XST16 = WinoXf<F>::XST16, PLANE = WinoXf<F>::VBYTES / 2;
+        const int oc = cq >> 1, odd = h & 1;
+        char* vb = vdst + odd * PLANE + oc * 256 + ((l16 ^ (2 * (oc & 3)) ^ (4 * odd)) * 16);
 #pragma unroll
-    for (int p = 0; p < 16; p++) *reinterpret_cast<f32x4*>(vb + p * XST) = out[p];
+        for (int p = 0; p < 16; p++) {
+            unsigned q[4];
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                // WinoXf::split16 of the channel pair (2e, 2e + 1), two values per instruction: the
+                // packed conversions round to nearest even as the scalar ones, the even channel in the
+                // low half
+                typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+                const f32x2 s = f32x2{out[p][2 * e], out[p][2 * e + 1]} * WINO16_SA;
+                const f16x2 h2 = __builtin_convertvector(s, f16x2);
+                const f16x2 l2 = __builtin_convertvector(s - __builtin_convertvector(h2, f32x2), f16x2);
+                const unsigned hi = __builtin_bit_cast(unsigned, h2), lo = __builtin_bit_cast(unsigned, l2);
+                // v_permlane16_swap_b32: the odd rows of hi change places with the even rows of lo, so an
+                // even lane group then holds (its hi, the next group's hi), an odd one (the previous
+                // group's lo, its lo): both in channel order
+                const auto sw = __builtin_amdgcn_permlane16_swap(hi, lo, false, false);
+                q[e] = sw[0];
+                q[2 + e] = sw[1];
+            }
+            *reinterpret_cast<uint4*>(vb + p * XST16) = make_uint4(q[0], q[1], q[2], q[3]);
+        }
+    } else {
+        char* vb = vdst + cq * 256 + ((l16 ^ (2 * (cq & 3))) * 16);
+#pragma unroll
+        for (int p = 0; p < 16; p++) *reinterpret_cast<f32x4*>(vb + p * XST) = out[p];
+    }
 }
 
 // wino_core: one Winograd conv of the board whose layer input is in ACT ([64 squares][F/4 + 2
@@ -523,36 +566,48 @@ __device__ __forceinline__ void wino_core(char* __restrict__ ldsb, int vbase,
 }
 
 // ====================================================================== split-f16 point GEMMs
-// wino_core_h16: wino_core for F = 256 with the 16 point GEMMs on v_mfma_f32_16x16x32_f16 (16 issue
+// wino_core_h16: wino_core (any WinoCfg<F>) with the 16 point GEMMs on v_mfma_f32_16x16x32_f16 (16 issue
 // cycles for K = 32, against 8 x 32 for the f32 MFMA).  Each f32 factor is scaled by a power of two
 // and split into two f16 (11-bit significands), x = hi + lo to 22 bits, and the product is
 // hi hi + hi lo + lo hi, accumulated in f32: the dropped lo lo term is below 2^-22 relative, less
 // than the rounding of the f32 accumulation (tools/split16_numerics.py).  Same tiling, ACT,
 // accumulator / output layout, residual and epilogue as wino_core (the MFMA C/D layout does not
 // depend on the input type); differences:
-//   V        two f16 planes per chunk (WinoXf::store16), the same 32 KB per 32-channel chunk;
-//   weights  [32-channel chunk][xi][co/16][hi, lo][64 lanes][8] f16 (net.hip winograd_split16), lane
+//   V        two f16 planes per chunk (WinoXf::store16), the same 1 KB per channel of the chunk;
+//   weights  [32-channel group][xi][co/16][hi, lo][64 lanes][8] f16 (net.hip winograd_split16), lane
 //            = co % 16 + 16 (ci % 32 / 8), scaled per conv by Sw: the same 4 bytes per weight;
-//   step     one point x 32 channels: 4 weight fragments (2 output fragments x hi, lo), 2 B
-//            fragments, 6 MFMAs; 16 steps per chunk;
+//   step     XS points x 32 channels (WinoRing<F, true>): per point 2 NN weight fragments (output
+//            fragments x hi, lo), 2 B fragments, 3 NN MFMAs.  F = 256: one point, the two output
+//            fragments' chains interleaved; F = 128, 64: two points, one chain each.  A chunk is
+//            CH / 32 groups of 32 channels x 16 points, in the weights' order (group, point);
+//   F = 128  the next chunk's transform one item per wave, the second wave of each SIMD pair half a
+//            chunk after the first (wino_core's schedule; its 16-step stagger does not fit in the 8
+//            steps of a chunk here);
+//   F = 64   the single 64-channel chunk (two groups) in the V buffer the caller chose; the first
+//            conv's transform is WinoXf::store16 (4 items per thread), every other conv's was done
+//            by the conv before it from registers (wino_xform_regs<F, true>);
 //   unscale  the conv's 1 / (Sa Sw), a power of two (exact), folded into the output transform's
 //            bias add as one packed FMA.
 template <int F>
 __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase,
                                               const __amdgpu_buffer_rsrc_t rW, const __amdgpu_buffer_rsrc_t rN,
                                               const float* __restrict__ bias, float unscale,
-                                              f32x4 (&wr)[WinoCfg<F>::PF][2][WinoCfg<F>::NN], int w, int lane,
-                                              f32x4 (&y)[WinoCfg<F>::NN][4], bool pre = false,
+                                              f32x4 (&wr)[WinoRing<F, true>::PF][WinoRing<F, true>::RX][WinoCfg<F>::NN],
+                                              int w, int lane, f32x4 (&y)[WinoCfg<F>::NN][4], bool pre = false,
                                               unsigned long long* tr = nullptr) {
-    static_assert(F == 256, "split-f16 core: 8 waves x 32 output channels");
     constexpr int CF = F / 16;
-    constexpr int NWV = WinoCfg<F>::NWV, NN = WinoCfg<F>::NN, CH = WinoCfg<F>::CH, PF = WinoCfg<F>::PF;
-    constexpr int VBYTES = CH * 1024, NCHUNK = F / CH, SPC = 16;     // one step per point
-    constexpr int STEPB = CF * 2 * 1024;                             // weight bytes of a step
-    // steps of B fragments read ahead: a step lasts ~700 cycles at the weight stream's rate, one is
-    // enough, and 2 spilled 12 more VGPRs per block (C3 A/B: tower 13.0-13.3 ms against 13.4-13.7)
-    constexpr int LA = 1;
-    static_assert(CH == 32 && SPC % PF == 0 && SPC % LA == 0, "ring slots must be compile-time");
+    constexpr int NWV = WinoCfg<F>::NWV, NN = WinoCfg<F>::NN, CH = WinoCfg<F>::CH;
+    constexpr int PF = WinoRing<F, true>::PF, XS = WinoRing<F, true>::XS;
+    // t = (32-channel group t / 16, point t % 16) pairs of a chunk; a ring step covers XS
+    constexpr int VBYTES = CH * 1024, NCHUNK = F / CH, SPC = (CH / 32) * 16, SPX = SPC / XS;
+    constexpr int XST16 = WinoXf<F>::XST16;                          // bytes of a point in a plane
+    constexpr int STEPB = CF * 2 * 1024;                             // weight bytes of a (group, point)
+    // ring steps of B fragments read ahead.  F = 256: a step lasts ~700 cycles at the weight stream's
+    // rate, one is enough, and 2 spilled 12 more VGPRs per block (C3 A/B: tower 13.0-13.3 ms against
+    // 13.4-13.7); a two-point step is 96 cycles of MFMA issue, below the LDS latency: 2 (with 1,
+    // tower32w_kernel<128> spilled 6 VGPRs in front of the chunk loop; with 2 it needs no scratch)
+    constexpr int LA = XS == 1 ? 1 : 2;
+    static_assert(CH % 32 == 0 && SPX % PF == 0 && SPX % LA == 0 && 16 % XS == 0, "ring slots must be compile-time");
     const int l16 = lane & 15, h = lane >> 4;
     const int vrd = h * 256 + ((l16 ^ (2 * h)) * 16);                // hi plane; lo: slot ^ 4, + VBYTES / 2
     const int vrl = VBYTES / 2 + h * 256 + ((l16 ^ (2 * h) ^ 4) * 16);
@@ -563,10 +618,14 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
     for (int x = 0; x < 16; x++)
 #pragma unroll
         for (int n = 0; n < NN; n++) {
-            f32x2 z0, z1;
-            asm volatile("v_mov_b64 %0, 0" : "=v"(z0));
-            asm volatile("v_mov_b64 %0, 0" : "=v"(z1));
-            acc[x][n] = f32x4{z0.x, z0.y, z1.x, z1.y};
+            if constexpr (F == 256) {   // accumulators in VGPRs: 64-bit moves (see wino_core)
+                f32x2 z0, z1;
+                asm volatile("v_mov_b64 %0, 0" : "=v"(z0));
+                asm volatile("v_mov_b64 %0, 0" : "=v"(z1));
+                acc[x][n] = f32x4{z0.x, z0.y, z1.x, z1.y};
+            } else {
+                acc[x][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
         }
     const int voff = wino16_voff<F>(w, lane);
     if (!pre) {   // chunk 0 not transformed by the caller
@@ -576,53 +635,95 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
         __syncthreads();
     }
     wino_stamp(tr, 1);
+    // B fragment of (group, point) t: octets 4 (t / 16) + h of point t % 16
+    auto boff = [](int t) { return (t / 16) * 1024 + (t % 16) * XST16; };
 #pragma unroll 1
     for (int c = 0; c < NCHUNK; c++) {
+        typename WinoXf<F>::Patch dn;
         const int vb = vbase + (c & 1) * VBYTES;
         const bool more = c + 1 < NCHUNK;
-        f16x8 bq[LA][2];
+        f16x8 bq[LA][XS][2];
 #pragma unroll
-        for (int i = 0; i < LA; i++) {
-            bq[i][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + i * 1024);
-            bq[i][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + i * 1024);
-        }
+        for (int i = 0; i < LA; i++)
 #pragma unroll
-        for (int st = 0; st < SPC; st++) {
-            const f16x8 bh = bq[st % LA][0], bl = bq[st % LA][1];
-            if (st + LA < SPC) {
-                bq[st % LA][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + (st + LA) * 1024);
-                bq[st % LA][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + (st + LA) * 1024);
+            for (int xs = 0; xs < XS; xs++) {
+                bq[i][xs][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(i * XS + xs));
+                bq[i][xs][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(i * XS + xs));
             }
-            f16x8 a[2][NN];
 #pragma unroll
-            for (int pl = 0; pl < 2; pl++)
+        for (int st = 0; st < SPX; st++) {
+            f16x8 bh[XS], bl[XS];
 #pragma unroll
-                for (int n = 0; n < NN; n++) a[pl][n] = __builtin_bit_cast(f16x8, wr[st % PF][pl][n]);
-            {
-                // ring step st + PF; past this conv's last step the refills read the next conv's first
-                const bool nxt = st + PF >= SPC && !more;
-                const int tn = c * SPC + st + PF;
-                const int to = nxt ? tn - NCHUNK * SPC : tn;
+            for (int xs = 0; xs < XS; xs++) {
+                bh[xs] = bq[st % LA][xs][0];
+                bl[xs] = bq[st % LA][xs][1];
+                if (st + LA < SPX) {
+                    bq[st % LA][xs][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff((st + LA) * XS + xs));
+                    bq[st % LA][xs][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff((st + LA) * XS + xs));
+                }
+            }
+            f16x8 a[XS][2][NN];
+#pragma unroll
+            for (int xs = 0; xs < XS; xs++)
 #pragma unroll
                 for (int pl = 0; pl < 2; pl++)
 #pragma unroll
-                    for (int n = 0; n < NN; n++)
-                        wr[st % PF][pl][n] = __builtin_bit_cast(
-                            f32x4, __builtin_amdgcn_raw_buffer_load_b128(nxt ? rN : rW, voff + (2 * n + pl) * 1024,
-                                                                         to * STEPB, 0));
+                    for (int n = 0; n < NN; n++) a[xs][pl][n] = __builtin_bit_cast(f16x8, wr[st % PF][2 * xs + pl][n]);
+            {
+                // ring step st + PF; past this conv's last step the refills read the next conv's first
+                const bool nxt = st + PF >= SPX && !more;
+                const int tn = c * SPX + st + PF;
+                const int to = (nxt ? tn - NCHUNK * SPX : tn) * XS;
+#pragma unroll
+                for (int xs = 0; xs < XS; xs++)
+#pragma unroll
+                    for (int pl = 0; pl < 2; pl++)
+#pragma unroll
+                        for (int n = 0; n < NN; n++)
+                            wr[st % PF][2 * xs + pl][n] = __builtin_bit_cast(
+                                f32x4, __builtin_amdgcn_raw_buffer_load_b128(nxt ? rN : rW, voff + (2 * n + pl) * 1024,
+                                                                             (to + xs) * STEPB, 0));
             }
             __builtin_amdgcn_sched_barrier(0);
-            // hi hi, hi lo, lo hi of each output fragment, the two fragments' chains interleaved
+            // hi hi, hi lo, lo hi of each (point, output fragment), the step's two chains interleaved
 #pragma unroll
-            for (int n = 0; n < NN; n++) acc[st][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][n], bh, acc[st][n], 0, 0, 0);
+            for (int xs = 0; xs < XS; xs++)
 #pragma unroll
-            for (int n = 0; n < NN; n++) acc[st][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][n], bl, acc[st][n], 0, 0, 0);
+                for (int n = 0; n < NN; n++) {
+                    const int x = (st * XS + xs) % 16;
+                    acc[x][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[xs][0][n], bh[xs], acc[x][n], 0, 0, 0);
+                }
 #pragma unroll
-            for (int n = 0; n < NN; n++) acc[st][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1][n], bh, acc[st][n], 0, 0, 0);
+            for (int xs = 0; xs < XS; xs++)
+#pragma unroll
+                for (int n = 0; n < NN; n++) {
+                    const int x = (st * XS + xs) % 16;
+                    acc[x][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[xs][0][n], bl[xs], acc[x][n], 0, 0, 0);
+                }
+#pragma unroll
+            for (int xs = 0; xs < XS; xs++)
+#pragma unroll
+                for (int n = 0; n < NN; n++) {
+                    const int x = (st * XS + xs) % 16;
+                    acc[x][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[xs][1][n], bh[xs], acc[x][n], 0, 0, 0);
+                }
             __builtin_amdgcn_sched_barrier(0);
-            if (st == 4) wino_stamp(tr, 20 + c);
-            // the next chunk's transform: as in wino_core, by the first wave of each SIMD pair
-            if (st == SPC - 1 && more && w < NWV / 2) xf.template both<true>(c + 1, (c + 1) & 1);
+            if (st == 4 / XS) wino_stamp(tr, 20 + c);
+            if constexpr (F == 256) {
+                // the next chunk's transform: as in wino_core, by the first wave of each SIMD pair
+                (void)dn;
+                if (st == SPX - 1 && more && w < NWV / 2) xf.template both<true>(c + 1, (c + 1) & 1);
+            } else if constexpr (NCHUNK > 1) {
+                constexpr int TSP = WINO_TSPLIT / XS, TSG = SPX / 2;
+                static_assert(TSP >= 1 && TSG + TSP < SPX, "the late waves' transform ends inside the chunk");
+                const bool late = w >= NWV / 2;
+                if (st == 0 && more && !late) xf.load(c + 1, dn);
+                if (st == TSG && more && late) xf.load(c + 1, dn);
+                if (st == TSP && more && !late) xf.store16((c + 1) & 1, dn);
+                if (st == TSG + TSP && more && late) xf.store16((c + 1) & 1, dn);
+            } else {
+                (void)dn;
+            }
         }
         wino_stamp(tr, 12 + c);
         if (more) __syncthreads();   // (none after the last chunk: see wino_core)
