@@ -9,7 +9,11 @@ Settles: the scale rule (Sa; Sw per conv = the largest power of two with Sw max|
 net.hip winograd_split16), the representable range (|V| <= 4 |x|, so |x| < 65504 / (4 Sa); the input
 scaled up until the error leaves the f32-product level), f16 subnormals kept or flushed, and the split
 source (U from its f64 value or from its rounded f32 value).
-Usage: python tools/split16_numerics.py [filters=256] [blocks=20]   (output: profiles/split16_numerics.txt)"""
+The last section, -- channel spread, gives every activation channel its own power-of-two scale (as a
+trained net's BatchNorm does; tests/netcases.py channel_rescaled) on 3x64 and 2x128 towers, 3 boards:
+the f32 paths are exactly scale invariant, the split-f16 path (one Sa, one Sw per conv) is not.
+Usage: python tools/split16_numerics.py [filters=256] [blocks=20]   (output: profiles/split16_numerics.txt)
+       python tools/split16_numerics.py spread      (that section alone: profiles/split16_numerics_spread.txt)"""
 import sys
 
 import numpy as np
@@ -90,6 +94,39 @@ def tower(x, ws, conv, dt):
     return h, amax
 
 
+def spread_section():
+    """Per-channel scales 2^k, k integer: s on the residual stream, t_b on block b's inner activation;
+    conv1' = 2^t_b[co] conv1 / 2^s[ci], conv2' = 2^s[co] conv2 / 2^t_b[ci] (the BatchNorm scale folded
+    into the conv, as net.hip fold_conv): the same function with the stream carrying 2^s times its
+    value.  Statistic: max |out - float64| over the tower's output, each channel in units of its own
+    scale 2^s[c] (at k = 0 the plain max abs error)."""
+    print("-- channel spread (3 boards; max abs error of the tower output against float64, in channel units;"
+          " Sa=64, U split from f64)")
+    print("%-8s %-10s %9s | %10s %12s %12s %14s" % ("tower", "k in", "max |act|", "direct f32", "Winograd f32", "split kept", "split flushed"))
+    r = np.random.default_rng(1)
+    for nb, f in ((3, 64), (2, 128)):
+        bound = 1.0 / np.sqrt(f * 9)
+        base = [r.uniform(-bound, bound, (f, f, 3, 3)) for _ in range(2 * nb)]
+        x = np.maximum(r.standard_normal((3, 8, 8, f)), 0)
+        for lo, hi in ((0, 0), (-3, 3), (-5, 5), (-8, 4)):
+            s = r.integers(lo, hi + 1, f)
+            ws = []
+            for b in range(nb):
+                t = r.integers(lo, hi + 1, f)
+                ws.append(base[2 * b] * (2.0 ** t)[:, None, None, None] / (2.0 ** s)[None, :, None, None])
+                ws.append(base[2 * b + 1] * (2.0 ** s)[:, None, None, None] / (2.0 ** t)[None, :, None, None])
+            xin = x * 2.0 ** s
+            ref, amax = tower(xin, ws, lambda h, w: conv_direct(h, w, np.float64), np.float64)
+            errs = []
+            for conv in (lambda h, w: conv_direct(h, w, np.float32), Conv("f32"), Conv("h16", 64), Conv("h16", 64, flush=True)):
+                out, _ = tower(xin.astype(np.float32), ws, conv, np.float32)
+                errs.append((np.abs(out - ref) / 2.0 ** s).max())
+            print("%-8s %-10s %9.1f | %10.1e %12.1e %12.1e %14.1e" % ("%dx%d" % (nb, f), "{0}" if lo == hi else "[%d,%d]" % (lo, hi), amax, *errs))
+
+
+if sys.argv[1:2] == ["spread"]:
+    spread_section()
+    sys.exit(0)
 F = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 NB = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 Bn = 4
@@ -124,3 +161,4 @@ for xs in (1 / 32, 8, 32, 64):
     report("F(2x2) f32 products", xs, Conv("f32"))
     report("split-f16 Sa=64", xs, Conv("h16", 64))
     report("split-f16 Sa=64, flushed", xs, Conv("h16", 64, flush=True))
+spread_section()
