@@ -5,8 +5,8 @@ training.rs, parameters.rs) over the C-ABI of libaz.so (include/az.h).
 """
 from . import _lib, parameters
 from .agent import AlphaZero, load_model, load_mpk, num_params, random_weights, save_mpk
-from .chess import (GameResult, GameState, IllegalMove, Position, index_to_move, move_to_index, play_move,
-                    to_tensor)
+from .chess import (GameResult, GameState, IllegalMove, Position, get_best_move, index_to_move, minimax_scores,
+                    move_to_index, play_move, to_tensor)
 from .memory import ReplayBuffer, TrainingSample
 from .training import (EpisodeStep, SelfPlay, Trainer, comm_unique_id, get_cyclical_lr, process_batch,
                        run_all_episodes, run_episode, train)
@@ -17,4 +17,4 @@ __all__ = ["AlphaZero", "load_model", "load_mpk", "save_mpk", "num_params", "ran
            "index_to_move", "move_to_index", "play_move", "to_tensor", "EpisodeStep", "SelfPlay", "Trainer", "comm_unique_id",
            "get_cyclical_lr", "process_batch", "train", "ReplayBuffer", "TrainingSample",
            "run_all_episodes", "run_episode", "BatchedSearch", "MCTree", "make_cfg", "parameters", "EvaluationResult", "Player",
-           "compute_elo_rankings", "compute_elos", "evaluate"]
+           "compute_elo_rankings", "compute_elos", "evaluate", "get_best_move", "minimax_scores"]

@@ -153,6 +153,9 @@ SIGNATURES = [
     ("az_trainer_time_exchanges", C.c_int, [C.c_void_p, C.c_int]),
     ("az_rules_probe", C.c_int, [C.c_int, P(AzPos), P(C.c_int32), C.c_int, P(AzPos), P(C.c_int32), P(C.c_int32),
                                  P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_uint64), P(C.c_float)]),
+    ("az_minimax_scores", C.c_int, [C.c_int, P(AzPos), C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), P(C.c_int32),
+                                    P(C.c_int32), P(C.c_int64)]),
+    ("az_minimax_best", C.c_int, [P(C.c_int32), C.c_int, C.c_float]),
 ]
 
 if not os.path.exists(LIB_PATH):

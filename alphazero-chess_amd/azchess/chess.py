@@ -193,3 +193,45 @@ def rules_probe(parents, actions, device=0):
                                  L.fptr(planes)))
     return dict(child=child, moves=mv, nmoves=nm, root_moves=rmv, root_n=rn, outcome=oc, in_check=chk,
                 fen_key=fk, planes=planes)
+
+
+DEVICE_HOST = -1                     # AZ_DEVICE_HOST: the host path of az_minimax_scores
+MINIMAX_MAX_DEPTH = 8
+
+
+def minimax_scores(positions, depth, device=0):
+    """az_minimax_scores: get_best_move's scoring (chess.rs:298-319) of every position at once, on GPU
+    `device` or, with device=-1, on the host.  positions: a list of Positions or a numpy az_pos array.
+    Returns (entries, nodes): entries[i] = (moves, promo, scores) int32 arrays over legal_moves() in
+    shakmaty order with the four promotion entries (promo 0, or 1 N / 2 B / 3 R / 4 Q; an
+    under-promotion carries the queen promotion's move index), scores[k] = -negamax(child, depth-1);
+    nodes[i] = negamax() invocations for position i."""
+    if not isinstance(positions, np.ndarray):
+        positions = positions_to_array(positions)
+    par = np.ascontiguousarray(positions, L.POS_DTYPE)
+    n = len(par)
+    mv = np.zeros((n, L.MAX_MOVES), np.int32)
+    pr = np.zeros((n, L.MAX_MOVES), np.int32)
+    sc = np.zeros((n, L.MAX_MOVES), np.int32)
+    nm = np.zeros(n, np.int32)
+    nodes = np.zeros(n, np.int64)
+    L.check(L.lib.az_minimax_scores(int(device), par.ctypes.data_as(C.POINTER(L.AzPos)), n, int(depth),
+                                    L.i32ptr(mv), L.i32ptr(pr), L.i32ptr(sc), L.i32ptr(nm),
+                                    nodes.ctypes.data_as(C.POINTER(C.c_int64))))
+    return [(mv[i, :nm[i]].copy(), pr[i, :nm[i]].copy(), sc[i, :nm[i]].copy()) for i in range(n)], nodes
+
+
+def minimax_best(scores, u):
+    """az_minimax_best: best_moves.choose (chess.rs:304-321) at the uniform u -- the ordinal of the
+    chosen entry among those with the maximal score, or -1 for an empty list."""
+    s = np.ascontiguousarray(scores, np.int32)
+    return int(L.lib.az_minimax_best(L.i32ptr(s), len(s), C.c_float(u)))
+
+
+def get_best_move(position, depth, u, device=0):
+    """chess.rs:298-322 followed by the arena's move_to_index (validation.rs:113): the move index the
+    MiniMax(depth) bot plays from `position`, or None without a legal move.  An under-promotion it
+    prefers comes out as the queen promotion's index (chess.rs:165-167)."""
+    (moves, _, scores), = minimax_scores([position], depth, device)[0]
+    k = minimax_best(scores, u)
+    return None if k < 0 else int(moves[k])

@@ -11,13 +11,17 @@ else rand 0.8 WeightedIndex over the policy (float32 cumulative sums).  thread_r
 a seeded stream per (seed, game, ply) so a match is reproducible.
 `compute_elo_rankings` / `compute_elos` are ratings.rs:5-28 and :113-143 (float32, 1000
 iterations of rate 8, player 0 pinned at the base Elo).
-The minimax and human players (chess.rs:248-420, validation.rs:91-117) are out of scope.
+A MiniMax(n) player (chess.rs:248-322, validation.rs:113) scores all of its games to move in one
+az_minimax_scores call -- the batched negamax kernels on the GPU, or the same search on the host
+with device=-1 -- and takes one of the best entries with the same seeded stream; it runs no network,
+so it adds nothing to num_inferences.  The human player (chess.rs:325-420, validation.rs:91-111) is
+out of scope.
 """
 from dataclasses import dataclass
 
 import numpy as np
 
-from .chess import GameState, play_move, to_tensor
+from .chess import GameState, minimax_best, minimax_scores, play_move, to_tensor
 from .parameters import EVALUATION_GAMES, NUM_SIMULATIONS, TEMPERATURE_ANNEALING
 from .tree import BatchedSearch
 
@@ -32,10 +36,10 @@ class EvaluationResult:             # validation.rs:12-19
     drawrate: float
 
 
-class Player:                       # validation.rs:21-27 (MctsModel, BaseModel, Random)
-    def __init__(self, kind, model=None):
-        assert kind in ("mcts", "base", "random")
-        self.kind, self.model = kind, model
+class Player:                       # validation.rs:21-27 (MctsModel, BaseModel, MiniMax, Random)
+    def __init__(self, kind, model=None, depth=None, device=None):
+        assert kind in ("mcts", "base", "random", "minimax")
+        self.kind, self.model, self.depth, self.device = kind, model, depth, device
 
     @staticmethod
     def mcts(model):
@@ -49,6 +53,11 @@ class Player:                       # validation.rs:21-27 (MctsModel, BaseModel,
     @staticmethod
     def random():
         return Player("random")
+
+    @staticmethod
+    def minimax(depth=4, device=None):
+        """Player::MiniMax(depth); device=None searches on evaluate's device, -1 on the host."""
+        return Player("minimax", depth=depth, device=device)
 
 
 def argmax_last(v):
@@ -115,6 +124,12 @@ def evaluate(player_1, player_2, games=EVALUATION_GAMES, sims=NUM_SIMULATIONS,
                 for g in gs:
                     legal = states[g].position.legal_indices()   # with under-promotion duplicates
                     actions[g] = int(legal[rng.integers(len(legal))])
+                continue
+            if p.kind == "minimax":
+                entries, _ = minimax_scores([states[g].position for g in gs], p.depth,
+                                            device if p.device is None else p.device)
+                for g, (moves, _, scores) in zip(gs, entries):
+                    actions[g] = int(moves[minimax_best(scores, choice_uniform(seed, g, ply))])
                 continue
             if p.kind == "mcts":
                 s = searches[id(p)]

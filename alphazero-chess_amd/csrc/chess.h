@@ -343,8 +343,9 @@ template <class Sink> AZ_HD int gen_legal(const Pos& p, Sink& sink, bool* in_che
 struct NullSink { AZ_HD void operator()(int) {} };
 
 // index_to_move (chess.rs:118-171, UciMove::to_move) + play_unchecked for an index known
-// to be legal. Under-promotion indices play the queen promotion (chess.rs:165-167).
-AZ_HD Pos play_index(const Pos& p, int idx) {
+// to be legal. Under-promotion indices play the queen promotion (chess.rs:165-167); the minimax
+// bot searches legal_moves()'s own under-promotions (chess.rs:286-289) and passes their role.
+AZ_HD Pos play_index(const Pos& p, int idx, int promo_role = QUEEN) {
     const int us = p.turn, them = us ^ 1;
     const int plane = idx >> 6, s = idx & 63;
     const int file = s & 7, crank = s >> 3;
@@ -388,7 +389,7 @@ AZ_HD Pos play_index(const Pos& p, int idx) {
             clr_them = cb;
         }
         const bool promo = role == PAWN && (tb & BACKRANKS);
-        const int placed = promo ? QUEEN : role;
+        const int placed = promo ? promo_role : role;
 #pragma unroll
         for (int r = 0; r < 6; r++) {
             if (r == role) role_clr[r] |= fb;

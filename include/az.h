@@ -339,6 +339,25 @@ int az_rules_probe(int device, const az_pos* parent, const int32_t* action, int 
                    int32_t* nmoves, int32_t* root_moves, int32_t* root_n, int32_t* outcome, int32_t* in_check,
                    uint64_t* fen_key, float* planes);
 
+/* ---- arena opponent: the MiniMax(n) bot, chess.rs:248-322 ---------------------------------- */
+#define AZ_DEVICE_HOST (-1)
+#define AZ_MINIMAX_MAX_DEPTH 8
+/* get_best_move's scoring for n positions at once (chess.rs:268-322). For position i: nmoves[i] = entries of legal_moves()
+ * in shakmaty order WITH the four promotion entries; moves[i][k] = move index (queen-promotion index for all four);
+ * promo[i][k] = 0 or the promoted role (1 N, 2 B, 3 R, 4 Q); scores[i][k] = -negamax(child, depth-1);
+ * nodes[i] (may be NULL) = negamax() invocations for that position (the root's children included, the root not).
+ * Arrays are [n][AZ_MAX_MOVES]; only the first nmoves[i] entries of a row are written, and nothing is written when
+ * the call fails.  device >= 0: the GPU kernels; AZ_DEVICE_HOST: the same definition on the host (at most 16
+ * threads).  depth in 1..AZ_MINIMAX_MAX_DEPTH; a position az_rules_probe would refuse, or one that lists more than
+ * AZ_MAX_MOVES entries, is an error.  The GPU path keeps the tree's upper levels in a buffer of
+ * AZ_MINIMAX_FRONTIER nodes (environment, read per call; default 1048576, at least 256): no result depends on it. */
+int az_minimax_scores(int device, const az_pos* pos, int n, int depth, int32_t* moves, int32_t* promo,
+                      int32_t* scores, int32_t* nmoves, int64_t* nodes);
+/* best_moves.choose (chess.rs:304-321) with the seeded u in [0,1) standing in for thread_rng: the entry ordinal of the
+ * min(floor(u*ties), ties-1)-th entry (the product in float), in list order, among those with the maximal score;
+ * -1 if nmoves == 0. */
+int az_minimax_best(const int32_t* scores, int nmoves, float u);
+
 #ifdef __cplusplus
 }
 #endif
