@@ -4,7 +4,8 @@ Host-side mirror of the reference's module surface (chess.rs, agent.rs, tree.rs,
 training.rs, parameters.rs) over the C-ABI of libaz.so (include/az.h).
 """
 from . import _lib, parameters
-from .agent import AlphaZero, load_model, load_mpk, num_params, random_weights, save_mpk
+from .agent import (AlphaZero, load_model, load_mpk, mx8_conv_probe, mx8_quantize, num_params, random_weights,
+                    save_mpk)
 from .chess import (GameResult, GameState, IllegalMove, Position, get_best_move, index_to_move, minimax_scores,
                     move_to_index, play_move, to_tensor)
 from .memory import ReplayBuffer, TrainingSample
@@ -17,4 +18,4 @@ __all__ = ["AlphaZero", "load_model", "load_mpk", "save_mpk", "num_params", "ran
            "index_to_move", "move_to_index", "play_move", "to_tensor", "EpisodeStep", "SelfPlay", "Trainer", "comm_unique_id",
            "get_cyclical_lr", "process_batch", "train", "ReplayBuffer", "TrainingSample",
            "run_all_episodes", "run_episode", "BatchedSearch", "MCTree", "make_cfg", "parameters", "EvaluationResult", "Player",
-           "compute_elo_rankings", "compute_elos", "evaluate", "get_best_move", "minimax_scores"]
+           "compute_elo_rankings", "compute_elos", "evaluate", "get_best_move", "minimax_scores", "mx8_quantize", "mx8_conv_probe"]

@@ -16,7 +16,7 @@ CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 ACTION_SPACE = 4096
 MAX_MOVES = 256
 ONGOING, DRAW, WHITE_WINS, BLACK_WINS, ILLEGAL = 0, 1, 2, 3, -1
-DTYPE_F32, DTYPE_BF16 = 0, 1
+DTYPE_F32, DTYPE_BF16, DTYPE_FP8 = 0, 1, 2
 EVAL_NET, EVAL_SYNTHETIC, EVAL_CALLBACK = 0, 1, 2
 
 
@@ -153,6 +153,10 @@ SIGNATURES = [
     ("az_trainer_time_exchanges", C.c_int, [C.c_void_p, C.c_int]),
     ("az_rules_probe", C.c_int, [C.c_int, P(AzPos), P(C.c_int32), C.c_int, P(AzPos), P(C.c_int32), P(C.c_int32),
                                  P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_uint64), P(C.c_float)]),
+    ("az_mx8_quantize", C.c_int, [P(C.c_float), C.c_size_t, P(C.c_uint8), P(C.c_uint8)]),
+    ("az_mx8_conv_probe", C.c_int, [C.c_int, C.c_int, C.c_int, P(C.c_uint8), P(C.c_uint8), P(C.c_uint8), P(C.c_uint8),
+                                    P(C.c_uint16), P(C.c_float), P(C.c_float), P(C.c_uint16), P(C.c_uint8),
+                                    P(C.c_uint8)]),
     ("az_minimax_scores", C.c_int, [C.c_int, P(AzPos), C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), P(C.c_int32),
                                     P(C.c_int32), P(C.c_int64)]),
     ("az_minimax_best", C.c_int, [P(C.c_int32), C.c_int, C.c_float]),

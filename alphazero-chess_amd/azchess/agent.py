@@ -71,6 +71,10 @@ def save_mpk(path, weights, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS):
     L.check(L.lib.az_net_save_mpk(str(path).encode(), int(blocks), int(filters), L.fptr(w), w.size))
 
 
+# the evaluation precisions of include/az.h: f32 (the reference's), and the opt-in bf16 and MX-fp8 modes
+DTYPES = {"f32": L.DTYPE_F32, "bf16": L.DTYPE_BF16, "fp8": L.DTYPE_FP8}
+
+
 def load_model(path, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, dtype="f32", device=0):
     """main.rs:109-116: AlphaZero::new().load_record(record)."""
     return AlphaZero(blocks, filters, weights=load_mpk(path, blocks, filters), dtype=dtype, device=device)
@@ -81,21 +85,23 @@ class AlphaZero:
 
     def __init__(self, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, weights=None, dtype="f32", device=0,
                  seed=SEED):
+        if dtype not in DTYPES:
+            raise ValueError("dtype must be one of %s, not %r" % (", ".join(sorted(DTYPES)), dtype))
         if weights is None:
             weights = random_weights(blocks, filters, seed)
         self.weights = np.ascontiguousarray(weights, np.float32)
         self.blocks, self.filters = blocks, filters
         self.dtype = dtype
-        desc = L.AzNetDesc(blocks, filters, L.DTYPE_BF16 if dtype == "bf16" else L.DTYPE_F32)
+        desc = L.AzNetDesc(blocks, filters, DTYPES[dtype])
         h = C.c_void_p()
         L.check(L.lib.az_net_create(C.byref(desc), L.fptr(self.weights), self.weights.size, device, C.byref(h)))
         self._h = h
-        # libaz runs the fused tower kernel (f32 or bf16) unless AZ_FUSED_TOWER=0
+        # libaz runs the fused tower kernel unless AZ_FUSED_TOWER=0 (an fp8 net has no other: creation fails)
         self.fused_tower = os.environ.get("AZ_FUSED_TOWER", "1") != "0"
 
     @property
     def tower_kernel(self):
-        """Which kernel evaluates this net (libaz's choice: fused f32 Winograd / f32 direct / bf16)."""
+        """Which kernel evaluates this net (libaz's choice: fused f32 Winograd / f32 direct / bf16 / MX-fp8)."""
         buf = C.create_string_buffer(128)
         L.check(L.lib.az_net_tower_kernel(self._h, buf, 128))
         return buf.value.decode()
@@ -121,3 +127,43 @@ class AlphaZero:
         val = np.zeros(n, np.float32)
         L.check(L.lib.az_net_forward(self._h, L.fptr(x), n, L.fptr(pol), L.fptr(val)))
         return pol, val
+
+
+def mx8_quantize(x):
+    """az_mx8_quantize, the MX-fp8 mode's host block quantiser: x float32, a multiple of 32 values in
+    blocks of 32 consecutive ones -> (e4m3fn codes uint8 of x's shape, E8M0 scale bytes uint8 [blocks])."""
+    x = np.ascontiguousarray(x, np.float32)
+    if x.size % 32:
+        raise ValueError("mx8_quantize: %d values are not whole blocks of 32" % x.size)
+    codes = np.empty(x.shape, np.uint8)
+    scales = np.empty(x.size // 32, np.uint8)
+    u8 = lambda a: a.ctypes.data_as(L.P(C.c_uint8))
+    L.check(L.lib.az_mx8_quantize(L.fptr(x), x.size // 32, u8(codes), u8(scales)))
+    return codes, scales
+
+
+def mx8_conv_probe(filters, act_codes, act_scales, w_codes, w_scales, bias, residual=None, device=0):
+    """az_mx8_conv_probe (test hook): one residual conv layer of tower8_kernel.  act_codes [n,64,F] /
+    act_scales [n,64,F/32] uint8, w_codes [F,F,3,3] / w_scales [F,9,F/32] uint8, bias [F] float32,
+    residual [n,64,F] bf16 bits (uint16) or None -> dict(acc float32 [n,64,F], codes, scales, and with a
+    residual bf16 = the output's bf16 bits)."""
+    F = int(filters)
+    a = np.ascontiguousarray(act_codes, np.uint8)
+    n = a.size // (64 * F)
+    s = np.ascontiguousarray(act_scales, np.uint8)
+    wc, wsc = np.ascontiguousarray(w_codes, np.uint8), np.ascontiguousarray(w_scales, np.uint8)
+    b = np.ascontiguousarray(bias, np.float32)
+    if a.size != n * 64 * F or s.size != n * 64 * F // 32 or wc.size != F * F * 9 or wsc.size != F * 9 * F // 32 or b.size != F:
+        raise ValueError("mx8_conv_probe: operand shapes do not match filters = %d" % F)
+    r = None if residual is None else np.ascontiguousarray(residual, np.uint16)
+    if r is not None and r.size != a.size:
+        raise ValueError("mx8_conv_probe: residual shape")
+    out = dict(acc=np.empty((n, 64, F), np.float32), codes=np.empty((n, 64, F), np.uint8),
+               scales=np.empty((n, 64, F // 32), np.uint8))
+    if r is not None:
+        out["bf16"] = np.empty((n, 64, F), np.uint16)
+    u8 = lambda x: x.ctypes.data_as(L.P(C.c_uint8))
+    u16 = lambda x: None if x is None else x.ctypes.data_as(L.P(C.c_uint16))
+    L.check(L.lib.az_mx8_conv_probe(int(device), F, n, u8(a), u8(s), u8(wc), u8(wsc), u16(r), L.fptr(b), L.fptr(out["acc"]),
+                                    u16(out.get("bf16")), u8(out["codes"]), u8(out["scales"])))
+    return out

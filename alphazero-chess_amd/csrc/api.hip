@@ -274,6 +274,7 @@ int az_net_tower_kernel(az_net* net, char* out, int cap) {
     std::string k;
     const std::string F = std::to_string(n->filters);
     if (!(n->fused && tower_supported(n))) k = "conv3x3_kernel (per layer) + heads_kernel";
+    else if (n->dtype == AZ_DTYPE_FP8) k = "tower8_kernel<" + F + "> (MX-fp8 e4m3, direct 3x3)";
     else if (n->dtype == AZ_DTYPE_BF16) k = "tower_kernel<" + F + "> (bf16, direct 3x3)";
     else if (wino_split16(n))
         k = "tower32w_kernel<" + F + "> (f32, Winograd F(2x2,3x3) residual convs, split-f16 MFMA products)";

@@ -162,6 +162,10 @@ struct NetDev {
     void* in_pk32 = nullptr;        // f32 Winograd nets: the input conv's weights with channels 16-18 of 4 taps packed per k-step (tower32w)
     size_t in_pk32_bytes = 0;
     void* head_frag32 = nullptr;    // the same conv as f32 A-fragments of v_mfma_f32_16x16x4_f32 (f32 fused tower)
+    // AZ_DTYPE_FP8 (tower8.hip): the residual convs back to back as e4m3 A-fragments, their E8M0 scale
+    // bytes and their folded biases [2*blocks][F]; conv_w / conv_b / conv_bytes hold the bf16 input conv only
+    void* w8 = nullptr; void* w8s = nullptr; float* b8 = nullptr;
+    size_t w8_bytes = 0, w8s_bytes = 0;
     size_t head_floats = 0;
     hipStream_t stream = nullptr;
     bool fused = true;              // use tower_forward when supported (AZ_FUSED_TOWER=0 disables)
@@ -223,6 +227,12 @@ bool sims_persistent_supported(const NetDev* n);
 int sims_persistent(const NetDev* n, const Engine& E, const SearchOut& so, int step0, int step1, hipStream_t st);
 int tower_forward(NetDev* n, const void* planes, const int* count, int rows, float* pol, float* val,
                   const SearchOut* so, hipStream_t st);
+// MX-fp8 tower (tower8.hip): the same launch contract as tower_forward, for AZ_DTYPE_FP8 nets
+int tower8_forward(NetDev* n, const void* planes, const int* count, int rows, float* pol, float* val,
+                   const SearchOut* so, hipStream_t st);
+// one BatchNorm-folded residual conv wf [co][ci][9], quantised by az_mx8_quantize per (co, tap, 32 ci)
+// and appended as fragments to the host copies of NetDev::w8 / w8s
+void mx8_append_conv(const std::vector<float>& wf, int F, std::vector<uint8_t>* w8, std::vector<uint8_t>* w8s);
 size_t act_bytes(int dtype);
 double net_flop_per_eval(int blocks, int filters);
 double net_tower_flop_per_eval(int blocks, int filters);

@@ -39,7 +39,8 @@ template <> struct DTraits<float> { static constexpr int CH_SLOT = 4; static con
 
 template <typename T> __device__ __forceinline__ float to_f(T v) { return (float)v; }
 
-size_t act_bytes(int dtype) { return dtype == AZ_DTYPE_BF16 ? 2 : 4; }
+// the planes the towers read: f32 for f32 nets, bf16 otherwise (the MX-fp8 tower keeps the bf16 input conv)
+size_t act_bytes(int dtype) { return dtype == AZ_DTYPE_F32 ? 4 : 2; }
 
 double net_tower_flop_per_eval(int B, int F) {
     return 2.0 * 64.0 * (171.0 * F + 18.0 * B * (double)F * F);
@@ -551,7 +552,13 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
     const int B = d->blocks, F = d->filters;
     if (!(F == 32 || F == 64 || F == 128 || F == 256)) return fail("filters must be 32, 64, 128 or 256");
     if (B < 0 || B > 64) return fail("blocks out of range");
-    if (d->dtype != AZ_DTYPE_F32 && d->dtype != AZ_DTYPE_BF16) return fail("dtype must be AZ_DTYPE_F32/BF16");
+    if (d->dtype != AZ_DTYPE_F32 && d->dtype != AZ_DTYPE_BF16 && d->dtype != AZ_DTYPE_FP8)
+        return fail("dtype must be AZ_DTYPE_F32, AZ_DTYPE_BF16 or AZ_DTYPE_FP8");
+    const bool fp8 = d->dtype == AZ_DTYPE_FP8;
+    if (fp8 && F != 128 && F != 256) return fail("AZ_DTYPE_FP8: the MX-fp8 tower supports 128 or 256 filters, not " + std::to_string(F));
+    if (fp8 && B > 40) return fail("AZ_DTYPE_FP8: at most 40 blocks");
+    if (fp8 && getenv("AZ_FUSED_TOWER") && atoi(getenv("AZ_FUSED_TOWER")) == 0)
+        return fail("AZ_DTYPE_FP8 has only the fused tower kernel (AZ_FUSED_TOWER=0 is set)");
     if (n != az_net_num_params(B, F)) return fail("weight count mismatch");
     AZ_HIP(hipSetDevice(device));
     NetDev* net = new NetDev();
@@ -561,6 +568,8 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
     if (const char* e = getenv("AZ_WINO_SPLIT16")) net->split16 = atoi(e);
     AZ_HIP(hipStreamCreateWithFlags(&net->stream, hipStreamNonBlocking));
     const float* p = wts;
+    std::vector<uint8_t> w8h, w8sh;      // fp8: the residual convs' fragments, scale bytes and biases, uploaded below
+    std::vector<float> b8h;
     auto fold_conv = [&](int cin, const float* w, const float* bias, const float* bn) {
         const float *gamma = bn, *beta = bn + F, *mean = bn + 2 * F, *var = bn + 3 * F;
         std::vector<float> wf((size_t)F * cin * 9);
@@ -570,11 +579,16 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
             for (int k = 0; k < cin * 9; k++) wf[(size_t)co * cin * 9 + k] = (float)(w[(size_t)co * cin * 9 + k] * sc);
             bf[co] = (float)(((double)bias[co] - mean[co]) * sc + beta[co]);
         }
+        if (fp8 && cin == F) {
+            mx8_append_conv(wf, F, &w8h, &w8sh);
+            b8h.insert(b8h.end(), bf.begin(), bf.end());
+            return 0;
+        }
         const int CIN = cin == 19 ? 32 : cin;
         void* dw = nullptr;
         float* db = nullptr;
         size_t bytes = 0;
-        if (d->dtype == AZ_DTYPE_BF16) {
+        if (d->dtype != AZ_DTYPE_F32) {
             auto s = swizzle_bf16(wf, F, cin, CIN);
             bytes = s.size() * 2;
             if (hipMalloc(&dw, bytes) != hipSuccess) return -1;
@@ -628,6 +642,16 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
             if (fold_conv(F, p, p + (size_t)F * F * 9, p + (size_t)F * F * 9 + F)) return fail("alloc conv");
             p += (size_t)F * F * 9 + F + 4 * F;
         }
+    }
+    if (fp8 && B > 0) {
+        AZ_HIP(hipMalloc(&net->w8, w8h.size()));
+        AZ_HIP(hipMemcpy(net->w8, w8h.data(), w8h.size(), hipMemcpyHostToDevice));
+        AZ_HIP(hipMalloc(&net->w8s, w8sh.size()));
+        AZ_HIP(hipMemcpy(net->w8s, w8sh.data(), w8sh.size(), hipMemcpyHostToDevice));
+        AZ_HIP(hipMalloc((void**)&net->b8, b8h.size() * 4));
+        AZ_HIP(hipMemcpy(net->b8, b8h.data(), b8h.size() * 4, hipMemcpyHostToDevice));
+        net->w8_bytes = w8h.size();
+        net->w8s_bytes = w8sh.size();
     }
     // heads
     const HeadLayout L = HeadLayout::make(F);
@@ -712,6 +736,7 @@ void net_destroy(NetDev* n) {
     (void)hipFree(n->head_frag);
     (void)hipFree(n->head_frag32);
     (void)hipFree(n->in_pk32);
+    (void)hipFree(n->w8); (void)hipFree(n->w8s); (void)hipFree(n->b8);
     (void)hipFree(n->x); (void)hipFree(n->h); (void)hipFree(n->planes);
     (void)hipFree(n->d_in); (void)hipFree(n->d_pol); (void)hipFree(n->d_val);
     if (n->stream) (void)hipStreamDestroy(n->stream);
@@ -772,7 +797,7 @@ int net_heads_search(NetDev* n, const void* x, const int* count, int rows, const
 int net_encode_rows(NetDev* n, const azc::Pos* npos, int NMAX, const int* row_game, const int* row_node,
                     const int* count, int rows, void* planes, hipStream_t st) {
     if (rows <= 0) return 0;
-    if (n->dtype == AZ_DTYPE_BF16)
+    if (n->dtype != AZ_DTYPE_F32)
         encode_rows_kernel<__bf16><<<rows, 64, 0, st>>>(npos, NMAX, row_game, row_node, count, rows, (__bf16*)planes);
     else
         encode_rows_kernel<float><<<rows, 64, 0, st>>>(npos, NMAX, row_game, row_node, count, rows, (float*)planes);
@@ -781,7 +806,7 @@ int net_encode_rows(NetDev* n, const azc::Pos* npos, int NMAX, const int* row_ga
 
 int net_planes_from_host_layout(NetDev* n, const float* d_in, int rows, void* planes, hipStream_t st) {
     if (rows <= 0) return 0;
-    if (n->dtype == AZ_DTYPE_BF16)
+    if (n->dtype != AZ_DTYPE_F32)
         planes_from_nchw_kernel<__bf16><<<rows, 64, 0, st>>>(d_in, rows, (__bf16*)planes);
     else
         planes_from_nchw_kernel<float><<<rows, 64, 0, st>>>(d_in, rows, (float*)planes);

@@ -75,7 +75,9 @@ int az_game_history(const az_game* g, int32_t* moves, int cap);     /* indices p
 int az_game_play(az_game* g, int32_t index);
 
 /* ---- network: agent.rs AlphaZero ------------------------------------------------- */
-enum { AZ_DTYPE_F32 = 0, AZ_DTYPE_BF16 = 1 };
+/* AZ_DTYPE_FP8: the opt-in MX-fp8 mode (OCP MX, e4m3fn elements with one E8M0 scale per 32 channels on
+ * the residual convs; 128 or 256 filters, fused tower only; README "Precision"). */
+enum { AZ_DTYPE_F32 = 0, AZ_DTYPE_BF16 = 1, AZ_DTYPE_FP8 = 2 };
 typedef struct { int blocks, filters, dtype; } az_net_desc;
 typedef struct az_net az_net;
 /* number of f32 parameters in the flat layout (see DESIGN.md "Weights"): burn module
@@ -86,7 +88,7 @@ size_t az_net_num_params(int blocks, int filters);
  * BatchNorm folded into the convs (inference mode, model.valid()). */
 int az_net_create(const az_net_desc* desc, const float* weights, size_t n, int device, az_net** out);
 int az_net_destroy(az_net* net);
-/* name of the kernel(s) that evaluate this net (fused f32 Winograd / f32 direct / bf16 / per-layer) */
+/* name of the kernel(s) that evaluate this net (fused f32 Winograd / f32 direct / bf16 / MX-fp8 / per-layer) */
 int az_net_tower_kernel(az_net* net, char* out, int cap);
 /* burn NamedMpkFileRecorder<FullPrecisionSettings> model files:
  * load_model (main.rs:109-116) -> flat weights for az_net_create / az_trainer_create, and
@@ -338,6 +340,25 @@ int az_replay_load(const char* path, int capacity, az_replay** out);
 int az_rules_probe(int device, const az_pos* parent, const int32_t* action, int n, az_pos* child, int32_t* moves,
                    int32_t* nmoves, int32_t* root_moves, int32_t* root_n, int32_t* outcome, int32_t* in_check,
                    uint64_t* fen_key, float* planes);
+
+/* ---- test hooks: the MX-fp8 mode's arithmetic (the engine never calls az_mx8_conv_probe) -------
+ * az_mx8_quantize: the host block quantiser az_net_create applies to the folded residual conv weights
+ * of an AZ_DTYPE_FP8 net.  x holds nblocks blocks of 32 consecutive finite f32; block b gets the E8M0
+ * byte scales[b] = 127 + clamp(floor(log2 max|x|) - 8, -127, 127) (an all-zero block: 127) and
+ * codes[32 b + i] = x / 2^(scales[b] - 127) rounded to nearest even on the e4m3fn grid, saturating at
+ * +-448 (a block with a non-finite value: scale 0xFF, codes 0x7F). */
+int az_mx8_quantize(const float* x, size_t nblocks, uint8_t* codes, uint8_t* scales);
+/* One residual 3x3 conv layer (filters = 128 or 256) of n boards through the device conv routine and
+ * epilogue tower8_kernel uses.  act_codes [n][64][F] / act_scales [n][64][F/32]: the input activation
+ * (square = rank'*8 + file, blocks of 32 channels); w_codes [F][F][3][3] / w_scales [F][9][F/32]: the
+ * weights (blocks = 32 input channels of one output channel and tap, tap = 3 ky + kx); bias [F] f32, the
+ * accumulators' start; residual [n][64][F] bf16 or NULL.  With a residual the layer is a block's second
+ * conv, y = relu(acc + residual); without, its first, y = relu(acc).  Outputs (any may be NULL): acc
+ * [n][64][F], the raw f32 accumulators; out_bf16 (residual form only), y rounded to bf16;
+ * out_codes / out_scales, y block-quantised as az_mx8_quantize does. */
+int az_mx8_conv_probe(int device, int filters, int n, const uint8_t* act_codes, const uint8_t* act_scales,
+                      const uint8_t* w_codes, const uint8_t* w_scales, const uint16_t* residual, const float* bias,
+                      float* acc, uint16_t* out_bf16, uint8_t* out_codes, uint8_t* out_scales);
 
 /* ---- arena opponent: the MiniMax(n) bot, chess.rs:248-322 ---------------------------------- */
 #define AZ_DEVICE_HOST (-1)
