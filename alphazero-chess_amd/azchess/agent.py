@@ -107,6 +107,12 @@ class AlphaZero:
         return buf.value.decode()
 
     @property
+    def wino_streamed_points(self):
+        """Winograd points per 32 input channels whose weights the split-f16 tower streams (16, or 12
+        with the third row derived: AZ_WINO_DERIVE); 0 when another kernel evaluates this net."""
+        return L.check(L.lib.az_net_wino_streamed_points(self._h))
+
+    @property
     def winograd(self):
         return "Winograd" in self.tower_kernel
 

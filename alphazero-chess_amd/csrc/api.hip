@@ -284,6 +284,16 @@ int az_net_tower_kernel(az_net* net, char* out, int cap) {
     return 0;
 }
 
+int az_net_wino_streamed_points(az_net* net) {
+    if (!net) return fail("null argument");
+    const NetDev* n = net->dev;
+    return n->fused && tower_supported(n) && wino_split16(n) ? n->wino_streamed : 0;
+}
+
+int az_wino16_pack(const float* folded, int filters, int streamed, uint16_t* out, size_t cap, float* unscale) {
+    return wino16_pack(folded, filters, streamed, out, cap, unscale);
+}
+
 static int ensure_scratch(NetDev* n, int rows) {
     if (rows <= n->scratch_rows) return 0;
     (void)hipFree(n->x); (void)hipFree(n->h); (void)hipFree(n->planes);

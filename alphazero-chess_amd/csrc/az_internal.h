@@ -17,6 +17,9 @@ static_assert(sizeof(azc::Pos) == sizeof(az_pos), "Pos == az_pos");
 #ifndef AZ_WINO_SPLIT16_DEFAULT
 #define AZ_WINO_SPLIT16_DEFAULT 1
 #endif
+#ifndef AZ_WINO_DERIVE_DEFAULT
+#define AZ_WINO_DERIVE_DEFAULT 1
+#endif
 
 namespace azi {
 
@@ -29,6 +32,11 @@ constexpr float WINO16_SA = 64.0f;
 static inline bool wino16_selected(int level, int filters) {
     return filters == 256 ? level >= 1 : (filters == 128 || filters == 64) && level >= 2;
 }
+
+// AZ_WINO_DERIVE (default AZ_WINO_DERIVE_DEFAULT): the split-f16 tower at 256 filters streams 12 of the
+// 16 Winograd points' weights and derives row 2 from the other three (wino.h wino_core_h16<F, 12>);
+// 0, and 128 / 64 filters at any value, stream all 16
+static inline int wino16_streamed(bool derive, int filters) { return derive && filters == 256 ? 12 : 16; }
 
 void set_error(const std::string& msg);
 int fail(const std::string& msg);
@@ -157,6 +165,8 @@ struct NetDev {
     std::vector<size_t> wino16_bytes;
     std::vector<float> wino16_us;
     int split16 = AZ_WINO_SPLIT16_DEFAULT;   // split-f16 point GEMMs in tower32w_kernel (env AZ_WINO_SPLIT16=0/1/2)
+    bool wino_derive = AZ_WINO_DERIVE_DEFAULT != 0;   // env AZ_WINO_DERIVE=0/1 (wino16_streamed)
+    int wino_streamed = 16;         // points per 32-channel group in wino16_w: 16, or 12 with row 2 derived
     float* head = nullptr;          // folded head weights (f32)
     void* head_frag = nullptr;      // 1x1 F->40 head conv as bf16 hi/lo MFMA A-fragments (fused tower)
     void* in_pk32 = nullptr;        // f32 Winograd nets: the input conv's weights with channels 16-18 of 4 taps packed per k-step (tower32w)
@@ -221,6 +231,8 @@ int net_planes_from_host_layout(NetDev* n, const float* d_in, int rows, void* pl
 bool tower_supported(const NetDev* n);
 bool wino_supported(const NetDev* n);   // f32, F >= 64, Winograd weights built: tower32w_kernel
 bool wino_split16(const NetDev* n);     // ... with split-f16 MFMA products (wino16_selected)
+// az_wino16_pack (net.hip winograd_split16 on the host): the u16 count, or < 0
+int wino16_pack(const float* wf, int F, int streamed, uint16_t* out, size_t cap, float* unscale);
 // persistent per-game simulation kernel (tower.hip, k_sims32w): simulation steps [step0, step1) of
 // every game, tree steps and Winograd evaluations in one workgroup per game, all backed up at the end
 bool sims_persistent_supported(const NetDev* n);

@@ -505,9 +505,14 @@ uint16_t f16_rne(double x, double* r) {
 // wino_core_h16 never reads past a conv's last step (its refills switch to the next conv's buffer,
 // whose first 8 steps exist at every F, or to an empty resource after the last conv, which reads 0),
 // and every refill is a buffer load bounded by the allocation's size.
-std::vector<uint16_t> winograd_split16(const std::vector<float>& wf, int F, float* unscale) {
+// streamed = 12 (wino_core_h16<F, 12>): G's rows satisfy r1 + r2 = r0 + r3, so U[2][b] = U[0][b] +
+// U[3][b] - U[1][b] and row 2 is left out; the kernel adds its products from the other three rows'
+// fragments.  Steps [ci/32][b][a in (0, 1, 3)]: the three sources of the derived point (2, b) are
+// consecutive; row 1 is stored negated (exact), so that all three derived terms are additions.  Sw is
+// still taken over all 16 values: the same unscale, and Sw |U[2][b]| stays in range.
+std::vector<uint16_t> winograd_split16(const float* wf, int F, int streamed, float* unscale) {
     static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    const int CF = F / 16, NSTEP = (F / 32) * 16;
+    const int CF = F / 16, NSTEP = (F / 32) * streamed;
     std::vector<double> U((size_t)F * F * 16);
     double umax = 0.0;
     for (size_t cc = 0; cc < (size_t)F * F; cc++) {
@@ -533,11 +538,14 @@ std::vector<uint16_t> winograd_split16(const std::vector<float>& wf, int F, floa
     for (int co = 0; co < F; co++)
         for (int ci = 0; ci < F; ci++)
             for (int x = 0; x < 16; x++) {
-                const double s = ldexp(U[((size_t)co * F + ci) * 16 + x], se);
+                const int a = x / 4, b = x % 4;
+                if (streamed == 12 && a == 2) continue;            // derived by the kernel
+                const double u = ldexp(U[((size_t)co * F + ci) * 16 + x], se);
+                const double s = streamed == 12 && a == 1 ? -u : u;
                 double hv, lv;
                 const uint16_t hi = f16_rne(s, &hv);
                 const uint16_t lo = f16_rne(s - hv, &lv);
-                const int step = (ci / 32) * 16 + x;
+                const int step = (ci / 32) * streamed + (streamed == 12 ? b * 3 + (a == 3 ? 2 : a) : x);
                 const int lane = (co % 16) + 16 * ((ci % 32) / 8);
                 const size_t at = ((((size_t)step * CF + co / 16) * 2) * 64 + lane) * 8 + ci % 8;
                 o[at] = hi;
@@ -566,6 +574,7 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
     if (const char* e = getenv("AZ_FUSED_TOWER")) net->fused = atoi(e) != 0;
     if (const char* e = getenv("AZ_WINOGRAD")) net->winograd = atoi(e) != 0;
     if (const char* e = getenv("AZ_WINO_SPLIT16")) net->split16 = atoi(e);
+    if (const char* e = getenv("AZ_WINO_DERIVE")) net->wino_derive = atoi(e) != 0;
     AZ_HIP(hipStreamCreateWithFlags(&net->stream, hipStreamNonBlocking));
     const float* p = wts;
     std::vector<uint8_t> w8h, w8sh;      // fp8: the residual convs' fragments, scale bytes and biases, uploaded below
@@ -620,7 +629,8 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
         }
         if (h16) {
             float us = 1.0f;
-            auto u = winograd_split16(wf, F, &us);
+            net->wino_streamed = wino16_streamed(net->wino_derive, F);
+            auto u = winograd_split16(wf.data(), F, net->wino_streamed, &us);
             void* du = nullptr;
             if (hipMalloc(&du, u.size() * 2) != hipSuccess) return -1;
             if (hipMemcpy(du, u.data(), u.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -1;
@@ -817,6 +827,20 @@ int synth_eval_rows(const int* count, int rows, const SearchOut& so, hipStream_t
     if (rows <= 0) return 0;
     synth_eval_kernel<<<(rows + 63) / 64, 64, 0, st>>>(count, rows, so);
     return hipGetLastError() == hipSuccess ? 0 : fail("synth launch failed");
+}
+
+int wino16_pack(const float* wf, int F, int streamed, uint16_t* out, size_t cap, float* unscale) {
+    if (!wf) return fail("null argument");
+    if (!(F == 64 || F == 128 || F == 256)) return fail("az_wino16_pack: filters must be 64, 128 or 256");
+    if (streamed != 16 && streamed != 12) return fail("az_wino16_pack: streamed points must be 16 or 12");
+    const size_t n = (size_t)((F / 32) * streamed + 2) * (F / 16) * 2 * 64 * 8;
+    if (!out) return (int)n;
+    if (cap < n) return fail("az_wino16_pack: output too small");
+    float us = 1.0f;
+    const std::vector<uint16_t> u = winograd_split16(wf, F, streamed, &us);
+    memcpy(out, u.data(), n * 2);
+    if (unscale) *unscale = us;
+    return (int)n;
 }
 
 }  // namespace azi

@@ -451,7 +451,7 @@ __device__ __forceinline__ unsigned long long* tt_slot(int w) {
 __device__ __forceinline__ unsigned long long* tt_slot(int) { return nullptr; }
 #endif
 
-template <int F, bool RESID, bool H16>
+template <int F, bool RESID, bool H16, int SP = 16>
 __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
                                           const __amdgpu_buffer_rsrc_t rW, const __amdgpu_buffer_rsrc_t rN,
                                           const float* __restrict__ bias, float unscale,
@@ -476,7 +476,7 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
     wino_stamp(tr, 0);
     // F = 64: the single chunk's V alternates between two buffers from conv to conv (vsel)
     const int vconv = vbase + (F == 64 ? vsel * VBYTES : 0);
-    if constexpr (H16) wino_core_h16<F>(ldsb, vconv, rW, rN, bias, unscale, wr, w, lane, y, pre_in, tr);
+    if constexpr (H16) wino_core_h16<F, SP>(ldsb, vconv, rW, rN, bias, unscale, wr, w, lane, y, pre_in, tr);
     else wino_core<F>(ldsb, vconv, rW, rN, bias, wr, w, lane, y, pre_in, tr);
     wino_stamp(tr, 10);
     f32x4 o[NN][4];
@@ -504,7 +504,7 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
             else
                 while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seq)
                     __builtin_amdgcn_s_sleep(1);
-            WinoXf<F>(ldsb, vbase, w, lane).template both<H16>(0, 0);
+            WinoXf<F>(ldsb, vbase, w, lane).template both<H16, H16 && SP == 12>(0, 0);
         }
     } else if constexpr (F == 64) {
         // F = 64: each wave's 16 output channels are a quarter of the next conv's single chunk;
@@ -519,8 +519,9 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
     __syncthreads();
 }
 
-// one board (batch row row0) through the Winograd f32 tower, all NWV waves of the workgroup
-template <int F, bool SEARCH, bool H16>
+// one board (batch row row0) through the Winograd f32 tower, all NWV waves of the workgroup; SP: the
+// split-f16 weights' streamed points per 32-channel group (wino_core_h16)
+template <int F, bool SEARCH, bool H16, int SP = 16>
 __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes, const TowerArgs& ta, int row0,
                                                       float* __restrict__ pol_out, float* __restrict__ val_out,
                                                       const SearchOut& so, int tid) {
@@ -583,7 +584,8 @@ __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes,
             for (int rx = 0; rx < RX; rx++)
 #pragma unroll
                 for (int n = 0; n < NN; n++) {
-                    // split-f16: rx = point rx / 2 of step i, its hi / lo plane (wino_core_h16)
+                    // split-f16: rx = point rx / 2 of step i, its hi / lo plane (wino_core_h16; the steps
+                    // are linear in the weights at either SP)
                     const int off = H16 ? (2 * n + rx % 2) * 1024 + (i * XS + rx / 2) * (F / 16) * 2048
                                         : n * 1024 + wino_toff<F>(0, i * XS + rx);
                     wring[i][rx][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff + off, 0, 0));
@@ -597,9 +599,9 @@ __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes,
         // F = 256 / 64: each conv transforms the next conv's chunk 0 at its end (conv_wino; C3 A/B
         // -0.3 % against the tail transform alone)
         constexpr bool PRE = F == 256 || F == 64;
-        conv_wino<F, false, H16>(ldsb, vbase, r1, r2, ta.b[1 + 2 * b], ta.wus[2 * b], wring, xres, w, lane, PRE && b > 0, PRE, 0, flag,
+        conv_wino<F, false, H16, SP>(ldsb, vbase, r1, r2, ta.b[1 + 2 * b], ta.wus[2 * b], wring, xres, w, lane, PRE && b > 0, PRE, 0, flag,
                             2 * b + 1, tr ? tr + 3 + 64 * b : nullptr);
-        conv_wino<F, true, H16>(ldsb, vbase, r2, r3, ta.b[2 + 2 * b], ta.wus[2 * b + 1], wring, xres, w, lane, PRE, PRE && b + 1 < ta.blocks,
+        conv_wino<F, true, H16, SP>(ldsb, vbase, r2, r3, ta.b[2 + 2 * b], ta.wus[2 * b + 1], wring, xres, w, lane, PRE, PRE && b + 1 < ta.blocks,
                            F == 64 ? 1 : 0, flag, 2 * b + 2, tr ? tr + 35 + 64 * b : nullptr);
     }
     heads_group<F, RSF, 1, NT, SEARCH, true, H16>(ldsb, reinterpret_cast<float*>(V), 0, 1, row0, tid, ta.head_frag32, ta.head,
@@ -607,13 +609,13 @@ __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes,
     wino_stamp(tr, 3 + 64 * 20);
 }
 
-template <int F, bool SEARCH, bool H16>
+template <int F, bool SEARCH, bool H16, int SP = 16>
 __global__ void __launch_bounds__(WinoCfg<F>::NWV * 64)
 tower32w_kernel(const float* __restrict__ planes, TowerArgs ta, const int* __restrict__ count_ptr, int rows,
                 float* __restrict__ pol_out, float* __restrict__ val_out, SearchOut so) {
     const int count = count_ptr ? min(load_fresh(count_ptr), rows) : rows;
     if ((int)blockIdx.x >= count) return;
-    tower32w_board<F, SEARCH, H16>(planes, ta, blockIdx.x, pol_out, val_out, so, threadIdx.x);
+    tower32w_board<F, SEARCH, H16, SP>(planes, ta, blockIdx.x, pol_out, val_out, so, threadIdx.x);
 }
 
 // k_sims32w: simulation steps [step0, step1) of one game per workgroup, with no grid-wide step
@@ -633,7 +635,7 @@ template <int F> struct SimsCfg<F, true> {
     static_assert(TowerCfg<F>::BPB == 1, "persistent bf16 kernel: one board per workgroup");
     static constexpr int NT = (F / (16 * TowerCfg<F>::NCO)) * TowerCfg<F>::WB * 64;
 };
-template <int F, bool BF16, bool H16 = false>
+template <int F, bool BF16, bool H16 = false, int SP = 16>
 __global__ void __launch_bounds__((SimsCfg<F, BF16>::NT))
 k_sims32w(Engine E, TowerArgs ta, SearchOut so, int step0, int step1) {
     __shared__ int s_kind;
@@ -681,7 +683,7 @@ k_sims32w(Engine E, TowerArgs ta, SearchOut so, int step0, int step1) {
         wino_stamp(tr, 1914);
         if (kind == X_ROW) {
             if constexpr (BF16) tower_board<F, true>(nullptr, ta, g, 1, nullptr, nullptr, so, tid);
-            else tower32w_board<F, true, H16>(nullptr, ta, g, nullptr, nullptr, so, tid);
+            else tower32w_board<F, true, H16, SP>(nullptr, ta, g, nullptr, nullptr, so, tid);
         }
         __syncthreads();
         wino_stamp(tr, 1915);
@@ -743,15 +745,16 @@ int sims_persistent(const NetDev* n, const Engine& E, const SearchOut& so, int s
         k_sims32w<64, true><<<E.G, SimsCfg<64, true>::NT, 0, st>>>(E, ta, so, step0, step1);
         return hipGetLastError() == hipSuccess ? 0 : fail("persistent simulation kernel launch failed");
     }
-#define AZ_SIMS32W(FF, H16)                                                                             \
+#define AZ_SIMS32W(FF, H16, SP)                                                                         \
     if (n->filters == FF) {                                                                            \
-        k_sims32w<FF, false, H16><<<E.G, SimsCfg<FF, false>::NT, 0, st>>>(E, ta, so, step0, step1);     \
+        k_sims32w<FF, false, H16, SP><<<E.G, SimsCfg<FF, false>::NT, 0, st>>>(E, ta, so, step0, step1); \
         return hipGetLastError() == hipSuccess ? 0 : fail("persistent simulation kernel launch failed"); \
     }
     if (wino_split16(n)) {
-        AZ_SIMS32W(256, true) AZ_SIMS32W(128, true) AZ_SIMS32W(64, true)
+        if (n->wino_streamed == 12) { AZ_SIMS32W(256, true, 12) }
+        AZ_SIMS32W(256, true, 16) AZ_SIMS32W(128, true, 16) AZ_SIMS32W(64, true, 16)
     }
-    AZ_SIMS32W(256, false) AZ_SIMS32W(128, false) AZ_SIMS32W(64, false)
+    AZ_SIMS32W(256, false, 16) AZ_SIMS32W(128, false, 16) AZ_SIMS32W(64, false, 16)
 #undef AZ_SIMS32W
     return fail("persistent simulation kernel: unsupported filters");
 }
@@ -785,18 +788,19 @@ int tower_forward(NetDev* n, const void* planes, const int* count, int rows, flo
         return hipGetLastError() == hipSuccess ? 0 : fail("f32 tower launch failed");                          \
     }
     if (n->dtype == AZ_DTYPE_F32) {
-#define AZ_TOWER32W(FF, H16)                                                                                  \
+#define AZ_TOWER32W(FF, H16, SP)                                                                              \
         if (n->filters == FF) {                                                                                \
             constexpr int NT = WinoCfg<FF>::NWV * 64;                                                          \
-            if (so) tower32w_kernel<FF, true, H16><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s); \
-            else tower32w_kernel<FF, false, H16><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s);  \
+            if (so) tower32w_kernel<FF, true, H16, SP><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s); \
+            else tower32w_kernel<FF, false, H16, SP><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s);  \
             return hipGetLastError() == hipSuccess ? 0 : fail("f32 Winograd tower launch failed");             \
         }
         if (wino_split16(n)) {
-            AZ_TOWER32W(256, true) AZ_TOWER32W(128, true) AZ_TOWER32W(64, true)
+            if (n->wino_streamed == 12) { AZ_TOWER32W(256, true, 12) }
+            AZ_TOWER32W(256, true, 16) AZ_TOWER32W(128, true, 16) AZ_TOWER32W(64, true, 16)
         }
         if (wino_supported(n)) {
-            AZ_TOWER32W(256, false) AZ_TOWER32W(128, false) AZ_TOWER32W(64, false)
+            AZ_TOWER32W(256, false, 16) AZ_TOWER32W(128, false, 16) AZ_TOWER32W(64, false, 16)
         }
 #undef AZ_TOWER32W
         AZ_TOWER32(256) AZ_TOWER32(128) AZ_TOWER32(64) AZ_TOWER32(32)

@@ -211,14 +211,14 @@ template <int F> struct WinoXf {
     }
     // the first NWV / 2 waves transform chunk c into V[buf] for all NWV waves (their own items and
     // those of the waves NWV / 2 later): F = 256 only (IT = 1, NWV = 8)
-    template <bool H16 = false> __device__ __forceinline__ void both(int c, int buf) const {
+    template <bool H16 = false, bool NEG1 = false> __device__ __forceinline__ void both(int c, int buf) const {
         static_assert(IT == 1 && NWV == 8, "two items per thread of the first half");
         Patch d0, d1;
         load(c, d0, 0);
         if constexpr (H16) {   // one item at a time: the deeper weight ring leaves no room for both patches
-            store16(buf, d0, 0);
+            store16<NEG1>(buf, d0, 0);
             load(c, d1, 1);
-            store16(buf, d1, 1);
+            store16<NEG1>(buf, d1, 1);
         } else {
             load(c, d1, 1);
             store(buf, d0, 0);
@@ -238,6 +238,8 @@ template <int F> struct WinoXf {
     // (an XOR by 8 left the hi and lo lanes of a pair on one bank: PMC 22 % of LDS cycles conflicts).
     // A value beyond the f16 range (|V| Sa >= 65520) splits into (inf, -inf): their products sum to
     // NaN, which every ReLU of the split-f16 tower keeps, the heads' included (tower.hip relu_nan).
+    // NEG1 (wino_core_h16 with 12 streamed points): the point row 1 (xi = 4..7) is written negated, to
+    // go with the negated weights of that row; exact, and (inf, -inf) stays a NaN-producing pair.
     static __device__ __forceinline__ unsigned split16(float v) {
         const float s = v * WINO16_SA;
         const _Float16 hi = (_Float16)s;
@@ -250,7 +252,7 @@ template <int F> struct WinoXf {
         return odd * (VBYTES / 2) + (tch >> 3) * 256 +
                (((4 * tty + ttx) ^ (2 * ((tch >> 3) & 3)) ^ (4 * odd)) * 16) + ((tch & 7) >> 1) * 4;
     }
-    __device__ __forceinline__ void store16(int buf, const Patch& d, int g = 0) const {
+    template <bool NEG1 = false> __device__ __forceinline__ void store16(int buf, const Patch& d, int g = 0) const {
         const int tl = vgpr_index(ttx);
         const f32x2 m = f32x2{tl > 0 ? 1.0f : 0.0f, tl < 3 ? 1.0f : 0.0f};
         // v_perm_b32 selectors: even lane (own.hi, other.hi), odd lane (other.lo, own.lo)
@@ -266,7 +268,8 @@ template <int F> struct WinoXf {
                 for (int rp = 0; rp < 2; rp++)
 #pragma unroll
                     for (int e = 0; e < 2; e++) {
-                        const unsigned own = split16(e ? v[k][rp].y : v[k][rp].x);
+                        const float pv = e ? v[k][rp].y : v[k][rp].x;
+                        const unsigned own = split16(NEG1 && 2 * rp + e == 1 ? -pv : pv);
                         // quad_perm [1, 0, 3, 2]: the other channel of the pair
                         const unsigned oth = (unsigned)__builtin_amdgcn_update_dpp(0, (int)own, 0xB1, 0xF, 0xF, true);
                         *reinterpret_cast<unsigned*>(vb + ((2 * rp + e) * 4 + k) * XST16) = __builtin_amdgcn_perm(oth, own, sel);
@@ -588,7 +591,16 @@ __device__ __forceinline__ void wino_core(char* __restrict__ ldsb, int vbase,
 //            by the conv before it from registers (wino_xform_regs<F, true>);
 //   unscale  the conv's 1 / (Sa Sw), a power of two (exact), folded into the output transform's
 //            bias add as one packed FMA.
-template <int F>
+//   SP = 12  (F = 256, AZ_WINO_DERIVE) 12 of the 16 points' weights are streamed, a chunk is 12 ring
+//            steps instead of 16.  G's rows satisfy r1 + r2 = r0 + r3, so U[2][b] = U[0][b] + U[3][b] -
+//            U[1][b], and by linearity M[2][b] = (U[0][b] + U[3][b] - U[1][b]) V[2][b].  The steps come
+//            in the order [b][a = 0, 1, 3] (net.hip winograd_split16); while the A fragments of (a, b)
+//            are in the ring for their own point they are used a second time against V[2][b], into
+//            the accumulators of point (2, b): 12 MFMAs per step, in a pipe that the weight stream
+//            leaves idle three quarters of the time.  Row 1 of the weights is stored negated and the
+//            input transform negates row 1 of V (WinoXf::store16<true>): the own product is unchanged
+//            and the derived point's three terms are all additions.
+template <int F, int SP = 16>
 __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase,
                                               const __amdgpu_buffer_rsrc_t rW, const __amdgpu_buffer_rsrc_t rN,
                                               const float* __restrict__ bias, float unscale,
@@ -599,7 +611,9 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
     constexpr int NWV = WinoCfg<F>::NWV, NN = WinoCfg<F>::NN, CH = WinoCfg<F>::CH;
     constexpr int PF = WinoRing<F, true>::PF, XS = WinoRing<F, true>::XS;
     // t = (32-channel group t / 16, point t % 16) pairs of a chunk; a ring step covers XS
-    constexpr int VBYTES = CH * 1024, NCHUNK = F / CH, SPC = (CH / 32) * 16, SPX = SPC / XS;
+    constexpr bool DER = SP == 12;
+    static_assert(SP == 16 || (DER && XS == 1 && CH == 32), "derived points: one point per step, one group per chunk");
+    constexpr int VBYTES = CH * 1024, NCHUNK = F / CH, SPC = (CH / 32) * 16, SPX = DER ? 12 : SPC / XS;
     constexpr int XST16 = WinoXf<F>::XST16;                          // bytes of a point in a plane
     constexpr int STEPB = CF * 2 * 1024;                             // weight bytes of a (group, point)
     // ring steps of B fragments read ahead.  F = 256: a step lasts ~700 cycles at the weight stream's
@@ -631,10 +645,13 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
     if (!pre) {   // chunk 0 not transformed by the caller
         typename WinoXf<F>::Patch d0;
         xf.load(0, d0);
-        xf.store16(0, d0);
+        xf.template store16<DER>(0, d0);
         __syncthreads();
     }
     wino_stamp(tr, 1);
+    // the (group, point) t of step st, point xs: the weights' order.  12 streamed points: column
+    // st / 3, row 0, 1, 3
+    auto tof = [](int st, int xs) { return DER ? 4 * ((st % 3) + (st % 3) / 2) + st / 3 : st * XS + xs; };
     // B fragment of (group, point) t: octets 4 (t / 16) + h of point t % 16
     auto boff = [](int t) { return (t / 16) * 1024 + (t % 16) * XST16; };
 #pragma unroll 1
@@ -647,9 +664,21 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
         for (int i = 0; i < LA; i++)
 #pragma unroll
             for (int xs = 0; xs < XS; xs++) {
-                bq[i][xs][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(i * XS + xs));
-                bq[i][xs][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(i * XS + xs));
+                bq[i][xs][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(tof(i, xs)));
+                bq[i][xs][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(tof(i, xs)));
             }
+        // 12 streamed points: the B fragments of the derived point (2, b), held for the three steps of
+        // column b and refilled for column b + 1 once that column's last products have issued (read
+        // inside every step after the own products, in the own point's registers, they spilled 8
+        // VGPRs fewer and left the LDS latency exposed once per step: C3 A/B tower 12.63 ms against
+        // 12.42)
+        f16x8 dq[2];
+        if constexpr (DER) {
+            dq[0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(8));
+            dq[1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(8));
+        } else {
+            (void)dq;
+        }
 #pragma unroll
         for (int st = 0; st < SPX; st++) {
             f16x8 bh[XS], bl[XS];
@@ -658,8 +687,8 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
                 bh[xs] = bq[st % LA][xs][0];
                 bl[xs] = bq[st % LA][xs][1];
                 if (st + LA < SPX) {
-                    bq[st % LA][xs][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff((st + LA) * XS + xs));
-                    bq[st % LA][xs][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff((st + LA) * XS + xs));
+                    bq[st % LA][xs][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(tof(st + LA, xs)));
+                    bq[st % LA][xs][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(tof(st + LA, xs)));
                 }
             }
             f16x8 a[XS][2][NN];
@@ -685,34 +714,35 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
                                                                              (to + xs) * STEPB, 0));
             }
             __builtin_amdgcn_sched_barrier(0);
-            // hi hi, hi lo, lo hi of each (point, output fragment), the step's two chains interleaved
+            // hi hi, hi lo, lo hi of each (point, output fragment), the step's two chains interleaved;
+            // 12 streamed points: the same A fragments also against V[2][st / 3], into the derived
+            // point's accumulators (four chains)
+            constexpr int NP = DER ? 2 : 1;
 #pragma unroll
-            for (int xs = 0; xs < XS; xs++)
+            for (int term = 0; term < 3; term++)
 #pragma unroll
-                for (int n = 0; n < NN; n++) {
-                    const int x = (st * XS + xs) % 16;
-                    acc[x][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[xs][0][n], bh[xs], acc[x][n], 0, 0, 0);
-                }
+                for (int xs = 0; xs < XS; xs++)
 #pragma unroll
-            for (int xs = 0; xs < XS; xs++)
+                    for (int pt = 0; pt < NP; pt++)
 #pragma unroll
-                for (int n = 0; n < NN; n++) {
-                    const int x = (st * XS + xs) % 16;
-                    acc[x][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[xs][0][n], bl[xs], acc[x][n], 0, 0, 0);
-                }
-#pragma unroll
-            for (int xs = 0; xs < XS; xs++)
-#pragma unroll
-                for (int n = 0; n < NN; n++) {
-                    const int x = (st * XS + xs) % 16;
-                    acc[x][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[xs][1][n], bh[xs], acc[x][n], 0, 0, 0);
-                }
+                        for (int n = 0; n < NN; n++) {
+                            const int x = pt ? 8 + st / 3 : tof(st, xs) % 16;
+                            const f16x8 av = a[xs][term == 2 ? 1 : 0][n];
+                            const f16x8 bv = pt ? dq[term == 1 ? 1 : 0] : (term == 1 ? bl[xs] : bh[xs]);
+                            acc[x][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc[x][n], 0, 0, 0);
+                        }
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (DER) {
+                if (st % 3 == 2 && st + 1 < SPX) {
+                    dq[0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(8 + (st + 1) / 3));
+                    dq[1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(8 + (st + 1) / 3));
+                }
+            }
             if (st == 4 / XS) wino_stamp(tr, 20 + c);
             if constexpr (F == 256) {
                 // the next chunk's transform: as in wino_core, by the first wave of each SIMD pair
                 (void)dn;
-                if (st == SPX - 1 && more && w < NWV / 2) xf.template both<true>(c + 1, (c + 1) & 1);
+                if (st == SPX - 1 && more && w < NWV / 2) xf.template both<true, DER>(c + 1, (c + 1) & 1);
             } else if constexpr (NCHUNK > 1) {
                 constexpr int TSP = WINO_TSPLIT / XS, TSG = SPX / 2;
                 static_assert(TSP >= 1 && TSG + TSP < SPX, "the late waves' transform ends inside the chunk");

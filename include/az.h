@@ -90,6 +90,10 @@ int az_net_create(const az_net_desc* desc, const float* weights, size_t n, int d
 int az_net_destroy(az_net* net);
 /* name of the kernel(s) that evaluate this net (fused f32 Winograd / f32 direct / bf16 / MX-fp8 / per-layer) */
 int az_net_tower_kernel(az_net* net, char* out, int cap);
+/* Winograd points whose weights the split-f16 tower streams per 32 input channels: 16, or 12 where the
+ * kernel derives the third row of points from the other three (AZ_WINO_DERIVE, 256 filters); 0 for a
+ * net that another kernel evaluates */
+int az_net_wino_streamed_points(az_net* net);
 /* burn NamedMpkFileRecorder<FullPrecisionSettings> model files:
  * load_model (main.rs:109-116) -> flat weights for az_net_create / az_trainer_create, and
  * model.save_file (training.rs:269-270) from flat weights.  out/w hold az_net_num_params floats. */
@@ -348,6 +352,16 @@ int az_rules_probe(int device, const az_pos* parent, const int32_t* action, int 
  * codes[32 b + i] = x / 2^(scales[b] - 127) rounded to nearest even on the e4m3fn grid, saturating at
  * +-448 (a block with a non-finite value: scale 0xFF, codes 0x7F). */
 int az_mx8_quantize(const float* x, size_t nblocks, uint8_t* codes, uint8_t* scales);
+/* The host packer of the split-f16 Winograd tower's residual conv weights (test hook; no device):
+ * folded [filters][filters][3][3], BatchNorm already folded in; filters 64, 128 or 256; streamed 16 or
+ * 12.  U = G g G^T in f64, scaled by Sw (the largest power of two <= 2^24 with Sw max|U| <= 32768 over
+ * all 16 points), split hi = f16(Sw U), lo = f16(Sw U - hi), as A fragments
+ * [ci/32][step][co/16][hi, lo][lane = co%16 + 16 (ci%32/8)][ci%8] and two zero steps at the end.
+ * streamed 16: step = point 4 a + b.  streamed 12: row a = 2 is left out (U[2][b] = U[0][b] + U[3][b] -
+ * U[1][b]), step = 3 b + (0, 1, 2 for a = 0, 1, 3), and row a = 1 is stored negated.  Returns the number
+ * of uint16 the stream holds (out NULL: that alone), < 0 on error; *unscale (may be NULL) =
+ * 1 / (64 Sw). */
+int az_wino16_pack(const float* folded, int filters, int streamed, uint16_t* out, size_t cap, float* unscale);
 /* One residual 3x3 conv layer (filters = 128 or 256) of n boards through the device conv routine and
  * epilogue tower8_kernel uses.  act_codes [n][64][F] / act_scales [n][64][F/32]: the input activation
  * (square = rank'*8 + file, blocks of 32 channels); w_codes [F][F][3][3] / w_scales [F][9][F/32]: the

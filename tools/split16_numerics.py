@@ -12,8 +12,12 @@ source (U from its f64 value or from its rounded f32 value).
 The last section, -- channel spread, gives every activation channel its own power-of-two scale (as a
 trained net's BatchNorm does; tests/netcases.py channel_rescaled) on 3x64 and 2x128 towers, 3 boards:
 the f32 paths are exactly scale invariant, the split-f16 path (one Sa, one Sw per conv) is not.
+The section -- derived points prices streaming 12 (or 9) of the 16 points' weights and deriving the
+rest (U[2][b] = U[0][b] + U[3][b] - U[1][b], wino.h wino_core_h16<F, 12>) on one 256x256 conv, products
+summed in float64 so that only the product error shows.
 Usage: python tools/split16_numerics.py [filters=256] [blocks=20]   (output: profiles/split16_numerics.txt)
-       python tools/split16_numerics.py spread      (that section alone: profiles/split16_numerics_spread.txt)"""
+       python tools/split16_numerics.py spread      (that section alone: profiles/split16_numerics_spread.txt)
+       python tools/split16_numerics.py derive      (that section alone: profiles/derive_numerics.txt)"""
 import sys
 
 import numpy as np
@@ -124,6 +128,47 @@ def spread_section():
             print("%-8s %-10s %9.1f | %10.1e %12.1e %12.1e %14.1e" % ("%dx%d" % (nb, f), "{0}" if lo == hi else "[%d,%d]" % (lo, hi), amax, *errs))
 
 
+def derive_section(F=256, sa=64.0):
+    """One conv, He-scaled random weights, ReLU'd normal input; rms relative error of Y against float64.
+    Split products are exact and summed in float64; a derived point sums the products of its three
+    (or nine) source points' split weights against its own V."""
+    print("-- derived points (one %dx%d conv, Sa=%g, the Sw rule over all 16 points, products summed in float64)" % (F, F, sa))
+    r = np.random.default_rng(7)
+    w = (r.standard_normal((F, F, 3, 3)) * np.sqrt(2.0 / (9 * F))).astype(np.float32)
+    x = np.maximum(r.standard_normal((1, 8, 8, F)), 0).astype(np.float32)
+    U = np.einsum('ik,ockl,jl->ijoc', G, w.astype(np.float64), G)
+    assert np.array_equal(U[2], U[0] + U[3] - U[1]), "row identity of G"
+    xp = np.zeros((1, 10, 10, F), np.float32)
+    xp[:, 1:-1, 1:-1] = x
+    d = np.stack([xp[:, 2 * t:2 * t + 4, 2 * u:2 * u + 4, :] for t in range(4) for u in range(4)], axis=1)
+    out = lambda M: np.einsum('ai,btijo,cj->btaco', AT.astype(np.float64), M, AT.astype(np.float64))
+    ref = out(np.einsum('ijoc,btijc->btijo', U, np.einsum('ia,btajc,kj->btikc', BT.astype(np.float64), d.astype(np.float64), BT.astype(np.float64))))
+    V = np.einsum('ia,btajc,kj->btikc', BT, d, BT).astype(np.float32)
+    rms = lambda y: np.sqrt(((y - ref) ** 2).mean() / (ref ** 2).mean())
+    se = sw_exp(U)
+    uh, ul = (p.astype(np.float64) for p in split(np.ldexp(U, se), False))
+    vh, vl = (p.astype(np.float64) for p in split((V * np.float32(sa)).astype(np.float64), False))
+    prod = lambda i, j, a, b: (np.einsum('oc,btc->bto', uh[i, j], vh[:, :, a, b]) + np.einsum('oc,btc->bto', uh[i, j], vl[:, :, a, b]) +
+                               np.einsum('oc,btc->bto', ul[i, j], vh[:, :, a, b]))
+    src = lambda k, derived: ((0, 1), (3, 1), (1, -1)) if derived and k == 2 else ((k, 1),)
+    base = None
+    for name, dr, dc in (("16 streamed points", False, False), ("12 streamed, row 2 derived", True, False), ("9 streamed, both dimensions derived", True, True)):
+        M = np.zeros((1, 16, 4, 4, F))
+        for a in range(4):
+            for b in range(4):
+                for i, si in src(a, dr):
+                    for j, sj in src(b, dc):
+                        M[:, :, a, b] += si * sj * prod(i, j, a, b)
+        e = rms(out(M * np.ldexp(1.0 / sa, -se)))
+        base = base or e
+        print("%-40s rms rel %.3e  (%.2fx)" % (name, e, e / base))
+    y32 = out(np.einsum('ijoc,btijc->btijo', U.astype(np.float32), V).astype(np.float64))
+    print("%-40s rms rel %.3e  (f32 products of the rounded f32 U, summed by numpy in f32)" % ("plain f32 evaluation of the same conv", rms(y32)))
+
+
+if sys.argv[1:2] == ["derive"]:
+    derive_section()
+    sys.exit(0)
 if sys.argv[1:2] == ["spread"]:
     spread_section()
     sys.exit(0)
