@@ -99,7 +99,9 @@ SIGNATURES = [
     ("az_net_destroy", C.c_int, [C.c_void_p]),
     ("az_net_tower_kernel", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("az_net_wino_streamed_points", C.c_int, [C.c_void_p]),
+    ("az_net_wino_accumulators", C.c_int, [C.c_void_p]),
     ("az_wino16_pack", C.c_int, [P(C.c_float), C.c_int, C.c_int, P(C.c_uint16), C.c_size_t, P(C.c_float)]),
+    ("az_wino16_pack_rows", C.c_int, [P(C.c_float), C.c_int, P(C.c_uint16), C.c_size_t, P(C.c_float)]),
     ("az_net_load_mpk",C.c_int, [C.c_char_p, C.c_int, C.c_int, P(C.c_float), C.c_size_t]),
     ("az_net_save_mpk", C.c_int, [C.c_char_p, C.c_int, C.c_int, P(C.c_float), C.c_size_t]),
     ("az_net_forward", C.c_int, [C.c_void_p, P(C.c_float), C.c_int, P(C.c_float), P(C.c_float)]),

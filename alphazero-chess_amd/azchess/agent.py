@@ -113,6 +113,13 @@ class AlphaZero:
         return L.check(L.lib.az_net_wino_streamed_points(self._h))
 
     @property
+    def wino_accumulators(self):
+        """Winograd-domain accumulators per output fragment of the split-f16 tower: 8 in the row-direct
+        form (AZ_WINO_ROWS: Winograd across columns, the tap rows direct), 16 otherwise; 0 when
+        another kernel evaluates this net."""
+        return L.check(L.lib.az_net_wino_accumulators(self._h))
+
+    @property
     def winograd(self):
         return "Winograd" in self.tower_kernel
 

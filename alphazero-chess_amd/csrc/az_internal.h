@@ -20,12 +20,19 @@ static_assert(sizeof(azc::Pos) == sizeof(az_pos), "Pos == az_pos");
 #ifndef AZ_WINO_DERIVE_DEFAULT
 #define AZ_WINO_DERIVE_DEFAULT 1
 #endif
+#ifndef AZ_WINO_ROWS_DEFAULT
+#define AZ_WINO_ROWS_DEFAULT 1
+#endif
+// weight ring steps of the row-direct form (wino.h WinoRing; C3 A/B of 2, 3, 4: DESIGN.md 5.4)
+#ifndef AZ_WINO_ROWS_PF
+#define AZ_WINO_ROWS_PF 4
+#endif
 
 namespace azi {
 
 // split-f16 products (wino.h wino_core_h16, net.hip winograd_split16): the activation scale Sa, a
 // power of two.  |V| <= 4 |x|, so the layer inputs must stay below 65504 / (4 Sa) = 255.8
-// (tools/split16_numerics.py: the scale rule)
+// (tools/split16_numerics.py: the scale rule); 511.7 in the row-direct form (wino16_rows below)
 constexpr float WINO16_SA = 64.0f;
 // AZ_WINO_SPLIT16 is a level: 0 no split-f16 products, 1 (the default) at 256 filters, 2 also at 128
 // and 64 filters (measured, not yet the default there: DESIGN.md 5.5)
@@ -37,6 +44,15 @@ static inline bool wino16_selected(int level, int filters) {
 // 16 Winograd points' weights and derives row 2 from the other three (wino.h wino_core_h16<F, 12>);
 // 0, and 128 / 64 filters at any value, stream all 16
 static inline int wino16_streamed(bool derive, int filters) { return derive && filters == 256 ? 12 : 16; }
+// AZ_WINO_ROWS (default AZ_WINO_ROWS_DEFAULT): where 12 planes are streamed, the row-direct form
+// (wino.h wino_core_h16<256, 12, true>: Winograd across columns, the three tap rows direct, 8
+// accumulators per output fragment); 0 the derived-row form (16 accumulators).  AZ_WINO_DERIVE=0
+// selects the 16-point kernel whatever AZ_WINO_ROWS says.  Its ring is WINO_ROWS_PF steps deep and its
+// weight stream ends in as many zero steps.  |D| <= 2 |x|: the layer inputs must stay below 65504 /
+// (2 Sa) = 511.7 (255.8 in the other two forms)
+constexpr int WINO_ROWS_PF = AZ_WINO_ROWS_PF;
+static_assert(12 % WINO_ROWS_PF == 0 && WINO_ROWS_PF >= 2, "the ring's slots must be compile-time");
+static inline bool wino16_rows(bool derive, bool rows, int filters) { return wino16_streamed(derive, filters) == 12 && rows; }
 
 void set_error(const std::string& msg);
 int fail(const std::string& msg);
@@ -167,6 +183,8 @@ struct NetDev {
     int split16 = AZ_WINO_SPLIT16_DEFAULT;   // split-f16 point GEMMs in tower32w_kernel (env AZ_WINO_SPLIT16=0/1/2)
     bool wino_derive = AZ_WINO_DERIVE_DEFAULT != 0;   // env AZ_WINO_DERIVE=0/1 (wino16_streamed)
     int wino_streamed = 16;         // points per 32-channel group in wino16_w: 16, or 12 with row 2 derived
+    bool wino_rows_env = AZ_WINO_ROWS_DEFAULT != 0;   // env AZ_WINO_ROWS=0/1 (wino16_rows)
+    bool wino_rows = false;         // wino16_w holds the row-direct stream (winograd_split16_rows)
     float* head = nullptr;          // folded head weights (f32)
     void* head_frag = nullptr;      // 1x1 F->40 head conv as bf16 hi/lo MFMA A-fragments (fused tower)
     void* in_pk32 = nullptr;        // f32 Winograd nets: the input conv's weights with channels 16-18 of 4 taps packed per k-step (tower32w)
@@ -233,6 +251,8 @@ bool wino_supported(const NetDev* n);   // f32, F >= 64, Winograd weights built:
 bool wino_split16(const NetDev* n);     // ... with split-f16 MFMA products (wino16_selected)
 // az_wino16_pack (net.hip winograd_split16 on the host): the u16 count, or < 0
 int wino16_pack(const float* wf, int F, int streamed, uint16_t* out, size_t cap, float* unscale);
+// az_wino16_pack_rows (net.hip winograd_split16_rows): the same for the row-direct stream, F = 256
+int wino16_pack_rows(const float* wf, int F, uint16_t* out, size_t cap, float* unscale);
 // persistent per-game simulation kernel (tower.hip, k_sims32w): simulation steps [step0, step1) of
 // every game, tree steps and Winograd evaluations in one workgroup per game, all backed up at the end
 bool sims_persistent_supported(const NetDev* n);

@@ -554,6 +554,50 @@ std::vector<uint16_t> winograd_split16(const float* wf, int F, int streamed, flo
     return o;
 }
 
+// The row-direct stream (wino.h wino_core_h16<256, 12, true>): W = g G^T (f64), the Winograd weight
+// transform across columns only, [k][b] for the 3 tap rows x 4 column points.  Sw is the largest power
+// of two (at most 2^24) with Sw max|W| <= 32768 over these 12 values; the same split and A-fragment
+// layout as winograd_split16, step = 3 b + k per 32 input channels, nothing negated, then WINO_ROWS_PF
+// zero steps (the ring's depth).  *unscale = 1 / (Sa Sw).
+std::vector<uint16_t> winograd_split16_rows(const float* wf, int F, float* unscale) {
+    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    const int CF = F / 16, NSTEP = (F / 32) * 12;
+    std::vector<double> W((size_t)F * F * 12);
+    double wmax = 0.0;
+    for (size_t cc = 0; cc < (size_t)F * F; cc++) {
+        const float* g = &wf[cc * 9];
+        for (int k = 0; k < 3; k++)
+            for (int b = 0; b < 4; b++) {
+                const double u = (double)g[k * 3 + 0] * G[b][0] + (double)g[k * 3 + 1] * G[b][1] + (double)g[k * 3 + 2] * G[b][2];
+                W[cc * 12 + k * 4 + b] = u;
+                if (fabs(u) > wmax) wmax = fabs(u);
+            }
+    }
+    int se = 24;
+    if (wmax > 0.0 && std::isfinite(wmax)) {
+        int e;
+        (void)frexp(wmax, &e);                                     // wmax < 2^e
+        se = 15 - e < 24 ? 15 - e : 24;
+    }
+    *unscale = (float)ldexp(1.0 / (double)WINO16_SA, -se);
+    std::vector<uint16_t> o((size_t)(NSTEP + WINO_ROWS_PF) * CF * 2 * 64 * 8, 0);
+    for (int co = 0; co < F; co++)
+        for (int ci = 0; ci < F; ci++)
+            for (int k = 0; k < 3; k++)
+                for (int b = 0; b < 4; b++) {
+                    const double s = ldexp(W[((size_t)co * F + ci) * 12 + k * 4 + b], se);
+                    double hv, lv;
+                    const uint16_t hi = f16_rne(s, &hv);
+                    const uint16_t lo = f16_rne(s - hv, &lv);
+                    const int step = (ci / 32) * 12 + 3 * b + k;
+                    const int lane = (co % 16) + 16 * ((ci % 32) / 8);
+                    const size_t at = ((((size_t)step * CF + co / 16) * 2) * 64 + lane) * 8 + ci % 8;
+                    o[at] = hi;
+                    o[at + 64 * 8] = lo;
+                }
+    return o;
+}
+
 }  // namespace
 
 int net_create(const az_net_desc* d, const float* wts, size_t n, int device, NetDev** out) {
@@ -575,6 +619,7 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
     if (const char* e = getenv("AZ_WINOGRAD")) net->winograd = atoi(e) != 0;
     if (const char* e = getenv("AZ_WINO_SPLIT16")) net->split16 = atoi(e);
     if (const char* e = getenv("AZ_WINO_DERIVE")) net->wino_derive = atoi(e) != 0;
+    if (const char* e = getenv("AZ_WINO_ROWS")) net->wino_rows_env = atoi(e) != 0;
     AZ_HIP(hipStreamCreateWithFlags(&net->stream, hipStreamNonBlocking));
     const float* p = wts;
     std::vector<uint8_t> w8h, w8sh;      // fp8: the residual convs' fragments, scale bytes and biases, uploaded below
@@ -630,7 +675,9 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
         if (h16) {
             float us = 1.0f;
             net->wino_streamed = wino16_streamed(net->wino_derive, F);
-            auto u = winograd_split16(wf.data(), F, net->wino_streamed, &us);
+            net->wino_rows = wino16_rows(net->wino_derive, net->wino_rows_env, F);
+            auto u = net->wino_rows ? winograd_split16_rows(wf.data(), F, &us)
+                                    : winograd_split16(wf.data(), F, net->wino_streamed, &us);
             void* du = nullptr;
             if (hipMalloc(&du, u.size() * 2) != hipSuccess) return -1;
             if (hipMemcpy(du, u.data(), u.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -1;
@@ -838,6 +885,19 @@ int wino16_pack(const float* wf, int F, int streamed, uint16_t* out, size_t cap,
     if (cap < n) return fail("az_wino16_pack: output too small");
     float us = 1.0f;
     const std::vector<uint16_t> u = winograd_split16(wf, F, streamed, &us);
+    memcpy(out, u.data(), n * 2);
+    if (unscale) *unscale = us;
+    return (int)n;
+}
+
+int wino16_pack_rows(const float* wf, int F, uint16_t* out, size_t cap, float* unscale) {
+    if (!wf) return fail("null argument");
+    if (F != 256) return fail("az_wino16_pack_rows: the row-direct stream is built for 256 filters only");
+    const size_t n = (size_t)((F / 32) * 12 + WINO_ROWS_PF) * (F / 16) * 2 * 64 * 8;
+    if (!out) return (int)n;
+    if (cap < n) return fail("az_wino16_pack_rows: output too small");
+    float us = 1.0f;
+    const std::vector<uint16_t> u = winograd_split16_rows(wf, F, &us);
     memcpy(out, u.data(), n * 2);
     if (unscale) *unscale = us;
     return (int)n;

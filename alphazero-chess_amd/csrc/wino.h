@@ -106,10 +106,13 @@ template <> struct WinoCfg<64> { static constexpr int NWV = 4, NN = 1, XS = 2, C
 // accumulator chains interleave), two points per step where it owns one (F = 128, 64: one point's
 // hi hi, hi lo, lo hi is a single dependent chain).  There a step is 6 MFMAs of 16 cycles, a third of
 // the f32 step, so the ring is 4 steps deep: the same ~400 cycles of MFMA issue ahead of the loads
-template <int F, bool H16> struct WinoRing {
+// ROWS (wino_core_h16's row-direct form, F = 256): 8 accumulators per output fragment instead of 16
+// leave room for a ring of WINO_ROWS_PF steps; the 16-point and derived forms keep 2 (with 4 they
+// spill 51-73 VGPRs)
+template <int F, bool H16, bool ROWS = false> struct WinoRing {
     static constexpr int XS = H16 ? (WinoCfg<F>::NN == 1 ? 2 : 1) : WinoCfg<F>::XS;
     static constexpr int RX = H16 ? 2 * XS : XS;
-    static constexpr int PF = H16 && WinoCfg<F>::NN == 1 ? 4 : WinoCfg<F>::PF;
+    static constexpr int PF = ROWS ? WINO_ROWS_PF : H16 && WinoCfg<F>::NN == 1 ? 4 : WinoCfg<F>::PF;
 };
 // Winograd weight fragment offsets: wave w's lane base (output fragments NN w..) and the byte
 // offset of ring step t (16-channel group kl = t / 16, point t % 16) of chunk cg
@@ -139,6 +142,8 @@ template <int F> __device__ __forceinline__ int wino16_voff(int w, int lane) {
 // zero squares before / after ACT (WINO_PAD_SQ), so every row offset is an instruction immediate;
 // the off-board columns (tl = 0: j = 0, tl = 3: j = 3) are read at a clamped on-board column (3 / 4:
 // keeps the 32-lane groups of each read on distinct banks) and multiplied by 0 in store.
+// the input transform's forms (WinoXf::store16)
+constexpr int WINO_XF_FULL = 0, WINO_XF_NEG1 = 1, WINO_XF_COLS = 2;
 template <int F> struct WinoXf {
     static constexpr int NWV = WinoCfg<F>::NWV, CH = WinoCfg<F>::CH, RS = F / 4 + 2;
     static constexpr int VBYTES = CH * 1024, XST = CH * 64, IT = CH * 16 / (NWV * 64);
@@ -192,6 +197,17 @@ template <int F> struct WinoXf {
         v[2][1] = pk_negx_sub(B[2], B[1]);
         v[3][1] = pk_negx_sub_m3(B[3], m, B[1]);
     }
+    // d B of one channel's patch, the column pass of xform on the raw rows: v[k][rp] = (D[2 rp][k],
+    // D[2 rp + 1][k]), 8 packed operations
+    static __device__ __forceinline__ void xform_cols(const f32x2 (&d)[4][2], f32x2 m, f32x2 (&v)[4][2]) {
+#pragma unroll
+        for (int rp = 0; rp < 2; rp++) {
+            v[0][rp] = pk_fma_m0_sub(d[0][rp], m, d[2][rp]);
+            v[1][rp] = pk_add(d[1][rp], d[2][rp]);
+            v[2][rp] = pk_sub(d[2][rp], d[1][rp]);
+            v[3][rp] = pk_sub_m3(d[3][rp], m, d[1][rp]);
+        }
+    }
     __device__ __forceinline__ void store(int buf, const Patch& d, int g = 0) const {
         const int tl = vgpr_index(ttx);
         const f32x2 m = f32x2{tl > 0 ? 1.0f : 0.0f, tl < 3 ? 1.0f : 0.0f};
@@ -211,14 +227,14 @@ template <int F> struct WinoXf {
     }
     // the first NWV / 2 waves transform chunk c into V[buf] for all NWV waves (their own items and
     // those of the waves NWV / 2 later): F = 256 only (IT = 1, NWV = 8)
-    template <bool H16 = false, bool NEG1 = false> __device__ __forceinline__ void both(int c, int buf) const {
+    template <bool H16 = false, int XF = WINO_XF_FULL> __device__ __forceinline__ void both(int c, int buf) const {
         static_assert(IT == 1 && NWV == 8, "two items per thread of the first half");
         Patch d0, d1;
         load(c, d0, 0);
         if constexpr (H16) {   // one item at a time: the deeper weight ring leaves no room for both patches
-            store16<NEG1>(buf, d0, 0);
+            store16<XF>(buf, d0, 0);
             load(c, d1, 1);
-            store16<NEG1>(buf, d1, 1);
+            store16<XF>(buf, d1, 1);
         } else {
             load(c, d1, 1);
             store(buf, d0, 0);
@@ -238,8 +254,11 @@ template <int F> struct WinoXf {
     // (an XOR by 8 left the hi and lo lanes of a pair on one bank: PMC 22 % of LDS cycles conflicts).
     // A value beyond the f16 range (|V| Sa >= 65520) splits into (inf, -inf): their products sum to
     // NaN, which every ReLU of the split-f16 tower keeps, the heads' included (tower.hip relu_nan).
-    // NEG1 (wino_core_h16 with 12 streamed points): the point row 1 (xi = 4..7) is written negated, to
-    // go with the negated weights of that row; exact, and (inf, -inf) stays a NaN-producing pair.
+    // XF = WINO_XF_NEG1 (wino_core_h16 with 12 streamed points): the point row 1 (xi = 4..7) is written
+    // negated, to go with the negated weights of that row; exact, and (inf, -inf) stays a NaN-producing
+    // pair.  XF = WINO_XF_COLS (the row-direct form): the column transform alone, D = d B (xform_cols),
+    // plane 4 i + b = patch row i, column point b; |D| <= 2 |x|.  Scale, split, pair swap and layout
+    // are the same.
     static __device__ __forceinline__ unsigned split16(float v) {
         const float s = v * WINO16_SA;
         const _Float16 hi = (_Float16)s;
@@ -252,7 +271,8 @@ template <int F> struct WinoXf {
         return odd * (VBYTES / 2) + (tch >> 3) * 256 +
                (((4 * tty + ttx) ^ (2 * ((tch >> 3) & 3)) ^ (4 * odd)) * 16) + ((tch & 7) >> 1) * 4;
     }
-    template <bool NEG1 = false> __device__ __forceinline__ void store16(int buf, const Patch& d, int g = 0) const {
+    template <int XF = WINO_XF_FULL> __device__ __forceinline__ void store16(int buf, const Patch& d, int g = 0) const {
+        constexpr bool NEG1 = XF == WINO_XF_NEG1;
         const int tl = vgpr_index(ttx);
         const f32x2 m = f32x2{tl > 0 ? 1.0f : 0.0f, tl < 3 ? 1.0f : 0.0f};
         // v_perm_b32 selectors: even lane (own.hi, other.hi), odd lane (other.lo, own.lo)
@@ -260,7 +280,8 @@ template <int F> struct WinoXf {
 #pragma unroll
         for (int it = 0; it < IT; it++) {
             f32x2 v[4][2];   // [column k][row pair]
-            xform(d[it], m, v);
+            if constexpr (XF == WINO_XF_COLS) xform_cols(d[it], m, v);
+            else xform(d[it], m, v);
             char* vb = ldsb + vbase + buf * VBYTES + vwr16(tchan(it, g));
 #pragma unroll
             for (int k = 0; k < 4; k++)
@@ -600,20 +621,31 @@ __device__ __forceinline__ void wino_core(char* __restrict__ ldsb, int vbase,
 //            leaves idle three quarters of the time.  Row 1 of the weights is stored negated and the
 //            input transform negates row 1 of V (WinoXf::store16<true>): the own product is unchanged
 //            and the derived point's three terms are all additions.
-template <int F, int SP = 16>
+//   ROWS     (F = 256, SP = 12, AZ_WINO_ROWS) Winograd across columns only, a direct 3-tap correlation
+//            across rows: W[k][b] = (g G^T)[k][b] for the 3 tap rows, D[i][b] = (d B)[i][b] for the 4 raw
+//            patch rows (WinoXf::xform_cols), and the output transform's row sums are accumulated
+//            directly: s0[b] = sum_k W[k][b] D[k][b], s1[b] = sum_k W[k][b] D[k + 1][b] -- 8 accumulators
+//            per output fragment instead of 16.  The same 12 streamed planes (step 3 b + k, nothing
+//            negated), 16 V planes (4 i + b) and 12 MFMAs per step in four chains as the derived form;
+//            the input transform loses its row pass, the output transform its first stage, and no
+//            product is derived.  The registers that frees hold a deeper ring (WinoRing).
+template <int F, int SP = 16, bool ROWS = false>
 __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase,
                                               const __amdgpu_buffer_rsrc_t rW, const __amdgpu_buffer_rsrc_t rN,
                                               const float* __restrict__ bias, float unscale,
-                                              f32x4 (&wr)[WinoRing<F, true>::PF][WinoRing<F, true>::RX][WinoCfg<F>::NN],
+                                              f32x4 (&wr)[WinoRing<F, true, ROWS>::PF][WinoRing<F, true>::RX][WinoCfg<F>::NN],
                                               int w, int lane, f32x4 (&y)[WinoCfg<F>::NN][4], bool pre = false,
                                               unsigned long long* tr = nullptr) {
     constexpr int CF = F / 16;
     constexpr int NWV = WinoCfg<F>::NWV, NN = WinoCfg<F>::NN, CH = WinoCfg<F>::CH;
-    constexpr int PF = WinoRing<F, true>::PF, XS = WinoRing<F, true>::XS;
+    constexpr int PF = WinoRing<F, true, ROWS>::PF, XS = WinoRing<F, true>::XS;
     // t = (32-channel group t / 16, point t % 16) pairs of a chunk; a ring step covers XS
-    constexpr bool DER = SP == 12;
-    static_assert(SP == 16 || (DER && XS == 1 && CH == 32), "derived points: one point per step, one group per chunk");
-    constexpr int VBYTES = CH * 1024, NCHUNK = F / CH, SPC = (CH / 32) * 16, SPX = DER ? 12 : SPC / XS;
+    constexpr bool DER = SP == 12 && !ROWS;
+    static_assert(SP == 16 || (SP == 12 && XS == 1 && CH == 32), "12 streamed planes: one per step, one group per chunk");
+    static_assert(!ROWS || (SP == 12 && F == 256), "the row-direct form: 256 filters, 12 streamed planes");
+    constexpr int NACC = ROWS ? 8 : 16;
+    constexpr int XFORM = ROWS ? WINO_XF_COLS : DER ? WINO_XF_NEG1 : WINO_XF_FULL;
+    constexpr int VBYTES = CH * 1024, NCHUNK = F / CH, SPC = (CH / 32) * 16, SPX = SP == 12 ? 12 : SPC / XS;
     constexpr int XST16 = WinoXf<F>::XST16;                          // bytes of a point in a plane
     constexpr int STEPB = CF * 2 * 1024;                             // weight bytes of a (group, point)
     // ring steps of B fragments read ahead.  F = 256: a step lasts ~700 cycles at the weight stream's
@@ -627,9 +659,9 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
     const int vrl = VBYTES / 2 + h * 256 + ((l16 ^ (2 * h) ^ 4) * 16);
     const WinoXf<F> xf(ldsb, vbase, w, lane);
     const int co0 = w * 16 * NN + h * 4;
-    f32x4 acc[16][NN];
+    f32x4 acc[NACC][NN];
 #pragma unroll
-    for (int x = 0; x < 16; x++)
+    for (int x = 0; x < NACC; x++)
 #pragma unroll
         for (int n = 0; n < NN; n++) {
             if constexpr (F == 256) {   // accumulators in VGPRs: 64-bit moves (see wino_core)
@@ -645,7 +677,7 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
     if (!pre) {   // chunk 0 not transformed by the caller
         typename WinoXf<F>::Patch d0;
         xf.load(0, d0);
-        xf.template store16<DER>(0, d0);
+        xf.template store16<XFORM>(0, d0);
         __syncthreads();
     }
     wino_stamp(tr, 1);
@@ -659,100 +691,158 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
         typename WinoXf<F>::Patch dn;
         const int vb = vbase + (c & 1) * VBYTES;
         const bool more = c + 1 < NCHUNK;
-        f16x8 bq[LA][XS][2];
+        if constexpr (ROWS) {
+            // row-direct form.  B fragments: a rolling window of three planes, numbered n = 4 b + i in the
+            // order the steps meet them (V point 4 i + b), slot n % 3.  Step (b, k) multiplies planes n0 =
+            // 4 b + k and n0 + 1; plane n0 + 2 is read at the top of the step into the slot the previous
+            // step freed, and after a column's last products the next column's second plane into the slot
+            // just freed: 24 VGPRs, every read at least a step ahead of its use
+            (void)dn;
+            f16x8 bw[3][2];
+            auto bread = [&](int n) {
+                const int pt = 4 * (n % 4) + n / 4;
+                bw[n % 3][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + pt * XST16);
+                bw[n % 3][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + pt * XST16);
+            };
+            bread(0);
+            bread(1);
 #pragma unroll
-        for (int i = 0; i < LA; i++)
-#pragma unroll
-            for (int xs = 0; xs < XS; xs++) {
-                bq[i][xs][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(tof(i, xs)));
-                bq[i][xs][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(tof(i, xs)));
-            }
-        // 12 streamed points: the B fragments of the derived point (2, b), held for the three steps of
-        // column b and refilled for column b + 1 once that column's last products have issued (read
-        // inside every step after the own products, in the own point's registers, they spilled 8
-        // VGPRs fewer and left the LDS latency exposed once per step: C3 A/B tower 12.63 ms against
-        // 12.42)
-        f16x8 dq[2];
-        if constexpr (DER) {
-            dq[0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(8));
-            dq[1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(8));
-        } else {
-            (void)dq;
-        }
-#pragma unroll
-        for (int st = 0; st < SPX; st++) {
-            f16x8 bh[XS], bl[XS];
-#pragma unroll
-            for (int xs = 0; xs < XS; xs++) {
-                bh[xs] = bq[st % LA][xs][0];
-                bl[xs] = bq[st % LA][xs][1];
-                if (st + LA < SPX) {
-                    bq[st % LA][xs][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(tof(st + LA, xs)));
-                    bq[st % LA][xs][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(tof(st + LA, xs)));
-                }
-            }
-            f16x8 a[XS][2][NN];
-#pragma unroll
-            for (int xs = 0; xs < XS; xs++)
+            for (int st = 0; st < SPX; st++) {
+                const int b = st / 3, n0 = 4 * b + st % 3;
+                if (n0 + 2 < 16) bread(n0 + 2);
+                f16x8 a[2][NN];
 #pragma unroll
                 for (int pl = 0; pl < 2; pl++)
 #pragma unroll
-                    for (int n = 0; n < NN; n++) a[xs][pl][n] = __builtin_bit_cast(f16x8, wr[st % PF][2 * xs + pl][n]);
-            {
-                // ring step st + PF; past this conv's last step the refills read the next conv's first
-                const bool nxt = st + PF >= SPX && !more;
-                const int tn = c * SPX + st + PF;
-                const int to = (nxt ? tn - NCHUNK * SPX : tn) * XS;
+                    for (int n = 0; n < NN; n++) a[pl][n] = __builtin_bit_cast(f16x8, wr[st % PF][pl][n]);
+                {
+                    // ring step st + PF; past this conv's last step the refills read the next conv's first
+                    const bool nxt = st + PF >= SPX && !more;
+                    const int tn = c * SPX + st + PF;
+                    const int to = nxt ? tn - NCHUNK * SPX : tn;
+#pragma unroll
+                    for (int pl = 0; pl < 2; pl++)
+#pragma unroll
+                        for (int n = 0; n < NN; n++)
+                            wr[st % PF][pl][n] = __builtin_bit_cast(
+                                f32x4, __builtin_amdgcn_raw_buffer_load_b128(nxt ? rN : rW, voff + (2 * n + pl) * 1024,
+                                                                             to * STEPB, 0));
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                // W[k][b] against D[k][b] into s0[b] and against D[k + 1][b] into s1[b]: hi hi, hi lo, lo hi
+                // of each, four chains interleaved
+#pragma unroll
+                for (int term = 0; term < 3; term++)
+#pragma unroll
+                    for (int pt = 0; pt < 2; pt++)
+#pragma unroll
+                        for (int n = 0; n < NN; n++) {
+                            const f16x8 av = a[term == 2 ? 1 : 0][n];
+                            const f16x8 bv = bw[(n0 + pt) % 3][term == 1 ? 1 : 0];
+                            acc[4 * pt + b][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc[4 * pt + b][n], 0, 0, 0);
+                        }
+                __builtin_amdgcn_sched_barrier(0);
+                if (st % 3 == 2 && st + 1 < SPX) bread(n0 + 3);
+                if (st == 4) wino_stamp(tr, 20 + c);
+                // the next chunk's transform: as in wino_core, by the first wave of each SIMD pair
+                if (st == SPX - 1 && more && w < NWV / 2) xf.template both<true, XFORM>(c + 1, (c + 1) & 1);
+            }
+        } else {
+            f16x8 bq[LA][XS][2];
+#pragma unroll
+            for (int i = 0; i < LA; i++)
+#pragma unroll
+                for (int xs = 0; xs < XS; xs++) {
+                    bq[i][xs][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(tof(i, xs)));
+                    bq[i][xs][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(tof(i, xs)));
+                }
+            // 12 streamed points: the B fragments of the derived point (2, b), held for the three steps of
+            // column b and refilled for column b + 1 once that column's last products have issued (read
+            // inside every step after the own products, in the own point's registers, they spilled 8
+            // VGPRs fewer and left the LDS latency exposed once per step: C3 A/B tower 12.63 ms against
+            // 12.42)
+            f16x8 dq[2];
+            if constexpr (DER) {
+                dq[0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(8));
+                dq[1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(8));
+            } else {
+                (void)dq;
+            }
+#pragma unroll
+            for (int st = 0; st < SPX; st++) {
+                f16x8 bh[XS], bl[XS];
+#pragma unroll
+                for (int xs = 0; xs < XS; xs++) {
+                    bh[xs] = bq[st % LA][xs][0];
+                    bl[xs] = bq[st % LA][xs][1];
+                    if (st + LA < SPX) {
+                        bq[st % LA][xs][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(tof(st + LA, xs)));
+                        bq[st % LA][xs][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(tof(st + LA, xs)));
+                    }
+                }
+                f16x8 a[XS][2][NN];
 #pragma unroll
                 for (int xs = 0; xs < XS; xs++)
 #pragma unroll
                     for (int pl = 0; pl < 2; pl++)
 #pragma unroll
-                        for (int n = 0; n < NN; n++)
-                            wr[st % PF][2 * xs + pl][n] = __builtin_bit_cast(
-                                f32x4, __builtin_amdgcn_raw_buffer_load_b128(nxt ? rN : rW, voff + (2 * n + pl) * 1024,
-                                                                             (to + xs) * STEPB, 0));
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // hi hi, hi lo, lo hi of each (point, output fragment), the step's two chains interleaved;
-            // 12 streamed points: the same A fragments also against V[2][st / 3], into the derived
-            // point's accumulators (four chains)
-            constexpr int NP = DER ? 2 : 1;
+                        for (int n = 0; n < NN; n++) a[xs][pl][n] = __builtin_bit_cast(f16x8, wr[st % PF][2 * xs + pl][n]);
+                {
+                    // ring step st + PF; past this conv's last step the refills read the next conv's first
+                    const bool nxt = st + PF >= SPX && !more;
+                    const int tn = c * SPX + st + PF;
+                    const int to = (nxt ? tn - NCHUNK * SPX : tn) * XS;
 #pragma unroll
-            for (int term = 0; term < 3; term++)
+                    for (int xs = 0; xs < XS; xs++)
 #pragma unroll
-                for (int xs = 0; xs < XS; xs++)
+                        for (int pl = 0; pl < 2; pl++)
 #pragma unroll
-                    for (int pt = 0; pt < NP; pt++)
-#pragma unroll
-                        for (int n = 0; n < NN; n++) {
-                            const int x = pt ? 8 + st / 3 : tof(st, xs) % 16;
-                            const f16x8 av = a[xs][term == 2 ? 1 : 0][n];
-                            const f16x8 bv = pt ? dq[term == 1 ? 1 : 0] : (term == 1 ? bl[xs] : bh[xs]);
-                            acc[x][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc[x][n], 0, 0, 0);
-                        }
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (DER) {
-                if (st % 3 == 2 && st + 1 < SPX) {
-                    dq[0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(8 + (st + 1) / 3));
-                    dq[1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(8 + (st + 1) / 3));
+                            for (int n = 0; n < NN; n++)
+                                wr[st % PF][2 * xs + pl][n] = __builtin_bit_cast(
+                                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(nxt ? rN : rW, voff + (2 * n + pl) * 1024,
+                                                                                 (to + xs) * STEPB, 0));
                 }
-            }
-            if (st == 4 / XS) wino_stamp(tr, 20 + c);
-            if constexpr (F == 256) {
-                // the next chunk's transform: as in wino_core, by the first wave of each SIMD pair
-                (void)dn;
-                if (st == SPX - 1 && more && w < NWV / 2) xf.template both<true, DER>(c + 1, (c + 1) & 1);
-            } else if constexpr (NCHUNK > 1) {
-                constexpr int TSP = WINO_TSPLIT / XS, TSG = SPX / 2;
-                static_assert(TSP >= 1 && TSG + TSP < SPX, "the late waves' transform ends inside the chunk");
-                const bool late = w >= NWV / 2;
-                if (st == 0 && more && !late) xf.load(c + 1, dn);
-                if (st == TSG && more && late) xf.load(c + 1, dn);
-                if (st == TSP && more && !late) xf.store16((c + 1) & 1, dn);
-                if (st == TSG + TSP && more && late) xf.store16((c + 1) & 1, dn);
-            } else {
-                (void)dn;
+                __builtin_amdgcn_sched_barrier(0);
+                // hi hi, hi lo, lo hi of each (point, output fragment), the step's two chains interleaved;
+                // 12 streamed points: the same A fragments also against V[2][st / 3], into the derived
+                // point's accumulators (four chains)
+                constexpr int NP = DER ? 2 : 1;
+#pragma unroll
+                for (int term = 0; term < 3; term++)
+#pragma unroll
+                    for (int xs = 0; xs < XS; xs++)
+#pragma unroll
+                        for (int pt = 0; pt < NP; pt++)
+#pragma unroll
+                            for (int n = 0; n < NN; n++) {
+                                const int x = pt ? 8 + st / 3 : tof(st, xs) % 16;
+                                const f16x8 av = a[xs][term == 2 ? 1 : 0][n];
+                                const f16x8 bv = pt ? dq[term == 1 ? 1 : 0] : (term == 1 ? bl[xs] : bh[xs]);
+                                acc[x][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc[x][n], 0, 0, 0);
+                            }
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (DER) {
+                    if (st % 3 == 2 && st + 1 < SPX) {
+                        dq[0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + boff(8 + (st + 1) / 3));
+                        dq[1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + boff(8 + (st + 1) / 3));
+                    }
+                }
+                if (st == 4 / XS) wino_stamp(tr, 20 + c);
+                if constexpr (F == 256) {
+                    // the next chunk's transform: as in wino_core, by the first wave of each SIMD pair
+                    (void)dn;
+                    if (st == SPX - 1 && more && w < NWV / 2) xf.template both<true, XFORM>(c + 1, (c + 1) & 1);
+                } else if constexpr (NCHUNK > 1) {
+                    constexpr int TSP = WINO_TSPLIT / XS, TSG = SPX / 2;
+                    static_assert(TSP >= 1 && TSG + TSP < SPX, "the late waves' transform ends inside the chunk");
+                    const bool late = w >= NWV / 2;
+                    if (st == 0 && more && !late) xf.load(c + 1, dn);
+                    if (st == TSG && more && late) xf.load(c + 1, dn);
+                    if (st == TSP && more && !late) xf.store16((c + 1) & 1, dn);
+                    if (st == TSG + TSP && more && late) xf.store16((c + 1) & 1, dn);
+                } else {
+                    (void)dn;
+                }
             }
         }
         wino_stamp(tr, 12 + c);
@@ -766,15 +856,20 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
         const f32x4 bb = bias ? *reinterpret_cast<const f32x4*>(bias + co0 + n * 16) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int p = 0; p < 2; p++) {
-            f32x2 m[16];
+            f32x2 m[NACC];
 #pragma unroll
-            for (int x = 0; x < 16; x++) m[x] = p ? f32x2{acc[x][n][2], acc[x][n][3]} : f32x2{acc[x][n][0], acc[x][n][1]};
+            for (int x = 0; x < NACC; x++) m[x] = p ? f32x2{acc[x][n][2], acc[x][n][3]} : f32x2{acc[x][n][0], acc[x][n][1]};
             const f32x2 br = p ? f32x2{bb[2], bb[3]} : f32x2{bb[0], bb[1]};
             f32x2 s0[4], s1[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                s0[j] = pk_add(pk_add(m[j], m[4 + j]), m[8 + j]);
-                s1[j] = pk_sub(pk_sub(m[4 + j], m[8 + j]), m[12 + j]);
+                if constexpr (ROWS) {   // the row sums were accumulated directly
+                    s0[j] = m[j];
+                    s1[j] = m[4 + j];
+                } else {
+                    s0[j] = pk_add(pk_add(m[j], m[4 + j]), m[8 + j]);
+                    s1[j] = pk_sub(pk_sub(m[4 + j], m[8 + j]), m[12 + j]);
+                }
             }
             const f32x2 q0 = pkc_fma(pk_add(pk_add(s0[0], s0[1]), s0[2]), us, br);
             const f32x2 q1 = pkc_fma(pk_sub(pk_sub(s0[1], s0[2]), s0[3]), us, br);

@@ -94,6 +94,10 @@ int az_net_tower_kernel(az_net* net, char* out, int cap);
  * kernel derives the third row of points from the other three (AZ_WINO_DERIVE, 256 filters); 0 for a
  * net that another kernel evaluates */
 int az_net_wino_streamed_points(az_net* net);
+/* Winograd-domain accumulators per output fragment of the split-f16 tower: 16 (all 16 points, streamed
+ * or derived), or 8 where the kernel is Winograd across columns only and sums the three tap rows
+ * directly (AZ_WINO_ROWS, 256 filters, 12 streamed planes); 0 for a net that another kernel evaluates */
+int az_net_wino_accumulators(az_net* net);
 /* burn NamedMpkFileRecorder<FullPrecisionSettings> model files:
  * load_model (main.rs:109-116) -> flat weights for az_net_create / az_trainer_create, and
  * model.save_file (training.rs:269-270) from flat weights.  out/w hold az_net_num_params floats. */
@@ -362,6 +366,12 @@ int az_mx8_quantize(const float* x, size_t nblocks, uint8_t* codes, uint8_t* sca
  * of uint16 the stream holds (out NULL: that alone), < 0 on error; *unscale (may be NULL) =
  * 1 / (64 Sw). */
 int az_wino16_pack(const float* folded, int filters, int streamed, uint16_t* out, size_t cap, float* unscale);
+/* The same for the row-direct stream (AZ_WINO_ROWS; filters 256 only, anything else is an error):
+ * W = g G^T in f64, [k][b] for the 3 tap rows x 4 column points, Sw the largest power of two <= 2^24
+ * with Sw max|W| <= 32768 over these 12 values, the same split and A-fragment layout, step = 3 b + k,
+ * nothing negated, and as many zero steps at the end as the kernel's weight ring is deep.  Returns the
+ * number of uint16 (out NULL: that alone), < 0 on error; *unscale (may be NULL) = 1 / (64 Sw). */
+int az_wino16_pack_rows(const float* folded, int filters, uint16_t* out, size_t cap, float* unscale);
 /* One residual 3x3 conv layer (filters = 128 or 256) of n boards through the device conv routine and
  * epilogue tower8_kernel uses.  act_codes [n][64][F] / act_scales [n][64][F/32]: the input activation
  * (square = rank'*8 + file, blocks of 32 channels); w_codes [F][F][3][3] / w_scales [F][9][F/32]: the

@@ -17,7 +17,8 @@ rest (U[2][b] = U[0][b] + U[3][b] - U[1][b], wino.h wino_core_h16<F, 12>) on one
 summed in float64 so that only the product error shows.
 Usage: python tools/split16_numerics.py [filters=256] [blocks=20]   (output: profiles/split16_numerics.txt)
        python tools/split16_numerics.py spread      (that section alone: profiles/split16_numerics_spread.txt)
-       python tools/split16_numerics.py derive      (that section alone: profiles/derive_numerics.txt)"""
+       python tools/split16_numerics.py derive      (that section alone: profiles/derive_numerics.txt)
+       python tools/split16_numerics.py rows        (the row-direct form, AZ_WINO_ROWS: profiles/rows_numerics.txt)"""
 import sys
 
 import numpy as np
@@ -166,8 +167,56 @@ def derive_section(F=256, sa=64.0):
     print("%-40s rms rel %.3e  (f32 products of the rounded f32 U, summed by numpy in f32)" % ("plain f32 evaluation of the same conv", rms(y32)))
 
 
+def rows_section(F=256, sa=64.0):
+    """The row-direct form (wino.h wino_core_h16<256, 12, true>) on derive_section's conv: W = g G^T
+    (3 tap rows x 4 column points, Sw over these 12 values), D = d B (4 raw rows x 4 column points),
+    s_r[b] = sum_k W[k][b] D[r + k][b], Y = s A; against the 16-point and the derived-row models."""
+    print("-- row-direct form (one %dx%d conv, Sa=%g, products summed in float64)" % (F, F, sa))
+    A64, B64 = AT.astype(np.float64), BT.astype(np.float64)
+    for seed in (7, 8):
+        r = np.random.default_rng(seed)
+        w = (r.standard_normal((F, F, 3, 3)) * np.sqrt(2.0 / (9 * F))).astype(np.float32)
+        x = np.maximum(r.standard_normal((1, 8, 8, F)), 0).astype(np.float32)
+        xp = np.zeros((1, 10, 10, F), np.float32)
+        xp[:, 1:-1, 1:-1] = x
+        d = np.stack([xp[:, 2 * t:2 * t + 4, 2 * u:2 * u + 4, :] for t in range(4) for u in range(4)], axis=1)
+        U = np.einsum('ik,ockl,jl->ijoc', G, w.astype(np.float64), G)
+        ref = np.einsum('ai,btijo,cj->btaco', A64, np.einsum('ijoc,btijc->btijo', U, np.einsum('ia,btajc,kj->btikc', B64, d.astype(np.float64), B64)), A64)
+        rms = lambda y: np.sqrt(((y - ref) ** 2).mean() / (ref ** 2).mean())
+        sp = lambda s: tuple(p.astype(np.float64) for p in split(s, False))
+        # 16 points and the derived row
+        V = np.einsum('ia,btajc,kj->btikc', BT, d, BT).astype(np.float32)
+        se = sw_exp(U)
+        uh, ul = sp(np.ldexp(U, se))
+        vh, vl = sp((V * np.float32(sa)).astype(np.float64))
+        pr = lambda i, a: (np.einsum('joc,btjc->btjo', uh[i], vh[:, :, a]) + np.einsum('joc,btjc->btjo', uh[i], vl[:, :, a]) +
+                           np.einsum('joc,btjc->btjo', ul[i], vh[:, :, a]))
+        M16 = np.stack([pr(a, a) for a in range(4)], axis=2)
+        M12 = M16.copy()
+        M12[:, :, 2] = pr(0, 2) + pr(3, 2) - pr(1, 2)
+        e16, e12 = (rms(np.einsum('ai,btijo,cj->btaco', A64, M * np.ldexp(1.0 / sa, -se), A64)) for M in (M16, M12))
+        # row-direct
+        W = np.einsum('ockl,jl->kjoc', w.astype(np.float64), G)
+        D = np.einsum('btajc,kj->btakc', d, BT).astype(np.float32)
+        sw = sw_exp(W)
+        wh, wl = sp(np.ldexp(W, sw))
+        dh, dl = sp((D * np.float32(sa)).astype(np.float64))
+        S = np.zeros((1, 16, 2, 4, F))
+        for rr in range(2):
+            for k in range(3):
+                for a, b in ((wh, dh), (wh, dl), (wl, dh)):
+                    S[:, :, rr] += np.einsum('joc,btjc->btjo', a[k], b[:, :, rr + k])
+        er = rms(np.einsum('btrjo,cj->btrco', S * np.ldexp(1.0 / sa, -sw), A64))
+        print("seed %d: 16 points %.3e   12 streamed, row 2 derived %.3e (%.2fx)   row-direct %.3e (%.2fx)   Sw 2^%d / 2^%d   "
+              "max|V| %.2f max|D| %.2f x max|x|" % (seed, e16, e12, e12 / e16, er, er / e16, se, sw,
+                                                  np.abs(V).max() / np.abs(x).max(), np.abs(D).max() / np.abs(x).max()))
+
+
 if sys.argv[1:2] == ["derive"]:
     derive_section()
+    sys.exit(0)
+if sys.argv[1:2] == ["rows"]:
+    rows_section()
     sys.exit(0)
 if sys.argv[1:2] == ["spread"]:
     spread_section()
