@@ -813,16 +813,6 @@ __global__ void finalize_sum_kernel(const float* __restrict__ part, int nblk, in
     if (lane == 0 && cown) dst[c] = s;
 }
 
-// the bias gradients of every BN-fed conv of the step in one launch (they are needed only by the
-// optimizer): blockIdx.y = BatchNorm j, its bn_back4 partials at part + j pstride, its gradient at
-// g + dst[j]
-__global__ void finalize_sum_batched_kernel(const float* __restrict__ part, size_t pstride, int nblk, int C,
-                                            const uint32_t* __restrict__ dst, float* __restrict__ g) {
-    FIN_CHANNEL();
-    const float s = part_sum(part + blockIdx.y * pstride, nblk, C, c, 0, lane);
-    if (lane == 0 && cown) g[dst[blockIdx.y] + c] = s;
-}
-
 // mean[c] = sum / R
 __global__ void finalize_mean_kernel(const float* __restrict__ part, int nblk, int C, int R, float* __restrict__ mean) {
     FIN_CHANNEL();
@@ -1017,10 +1007,8 @@ __global__ void __launch_bounds__(256) bn_back4_kernel(const float* __restrict__
                                                        const float* __restrict__ mean, const float* __restrict__ stdv,
                                                        const float* __restrict__ gamma, const float* __restrict__ dgamma,
                                                        const float* __restrict__ dbeta, float* __restrict__ dy,
-                                                       float* __restrict__ dres, float* __restrict__ bsum,
-                                                       const float* __restrict__ nglob) {
+                                                       float* __restrict__ dres, const float* __restrict__ nglob) {
     const int cq = C / 4, c = 4 * (threadIdx.x % cq), rs = 256 / cq;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);   // bsum: this thread's rows of dy, in order
     const float invR = 1.0f / (nglob ? nglob[vgpr_index(0)] : (float)R);   // sharded batch: all ranks' rows (vector load)
     const float4 mu = *reinterpret_cast<const float4*>(mean + c), sd = *reinterpret_cast<const float4*>(stdv + c);
     const float4 ga = *reinterpret_cast<const float4*>(gamma + c), dg = *reinterpret_cast<const float4*>(dgamma + c);
@@ -1037,23 +1025,37 @@ __global__ void __launch_bounds__(256) bn_back4_kernel(const float* __restrict__
                                       (ga.w / sd.w) * (dz.w - db.w * invR - ((y.w - mu.w) / sd.w) * dg.w * invR));
         *reinterpret_cast<float4*>(dy + o) = d4;
         if (dres) *reinterpret_cast<float4*>(dres + o) = dz;
-        acc.x += d4.x; acc.y += d4.y; acc.z += d4.z; acc.w += d4.w;
     }
-    // the conv bias gradient (sum of dy over rows) as per-workgroup partials in the column-sum
-    // layout part[block][2][C] (finalize_sum_kernel), instead of another pass over dy
-    if (bsum) {
-        __shared__ float4 red[256];
-        red[threadIdx.x] = acc;
-        __syncthreads();
-        if ((int)threadIdx.x < cq) {
-            float4 a = red[threadIdx.x];
-            for (int k = 1; k < rs; k++) {
-                const float4 b = red[k * cq + threadIdx.x];
-                a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-            }
-            *reinterpret_cast<float4*>(bsum + (size_t)blockIdx.x * 2 * C + c) = a;
-        }
-    }
+}
+
+// The bias gradient of a conv in front of a BatchNorm: the sum over this rank's rows of
+// dy = gamma / std (dz - dbeta / n - yhat dgamma / n).  The yhat term sums to gamma / std (dgamma / n)
+// sum(yhat), and sum(yhat) = 0 identically -- but with the batch mean rounded to float only to
+// rows x ulp(mean) / std, which left 1e-4 where the exact gradient is 0 at |mean| = 2^8 std.  So the
+// term is left out of the sum: dst = gamma / std (dbl - R dbeta / n), dbl this rank's sum of dz, dbeta
+// all ranks' (sharded batch: the ranks' dst add up to the rounding of one division; else dbl = dbeta).
+__device__ __forceinline__ float bn_bias_grad(float gamma, float sd, float dbl, float dbeta, float R, float invR) {
+    return (gamma / sd) * (dbl - R * (dbeta * invR));
+}
+__global__ void bn_bias_grad_kernel(const float* __restrict__ gamma, const float* __restrict__ stdv,
+                                    const float* __restrict__ dbl, const float* __restrict__ dbeta,
+                                    const float* __restrict__ nglob, int R, int C, float* __restrict__ dst) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const float invR = 1.0f / (nglob ? nglob[vgpr_index(0)] : (float)R);
+    dst[c] = bn_bias_grad(gamma[c], stdv[c], dbl[c], dbeta[c], (float)R, invR);
+}
+// the same for every BN-fed conv of a rank-local batch in one launch at the end of the backward (the
+// bias gradients are needed only by the optimizer; a launch per BatchNorm cost 0.4 % of the 20x256
+// step): blockIdx.y = BatchNorm j, tab[j] = {BN offset, bias offset, channels, BN index}; dbl = dbeta
+// = the gradient's dbeta
+__global__ void bn_bias_grad_batched_kernel(const float* __restrict__ p, const float* __restrict__ bstd, int slot,
+                                            float* __restrict__ g, const uint4* __restrict__ tab, int R) {
+    const uint4 t = tab[blockIdx.y];
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= (int)t.z) return;
+    const float d = g[t.x + t.z + c];
+    g[t.y + c] = bn_bias_grad(p[t.x + c], bstd[(size_t)t.w * slot + c], d, d, (float)R, 1.0f / (float)R);
 }
 
 // planes [B][19][64] (to_tensor layout, chess.rs:191-245) -> X0 [B*64][X0C] (channels >= 19 zero;
@@ -1200,11 +1202,10 @@ struct BnIn {
 };
 // XIN 2 (data-grad convs): the conv's input dy is the BatchNorm backward of X = dout (the ReLU
 // output's gradient), computed while the board's rows are staged (bn_back4_kernel's arithmetic,
-// element for element) and written out for the weight grad; dres (BN2) gets dz; bsum gets the
-// board's sum of dy per channel (the producing conv's bias gradient, summed over boards later)
+// element for element) and written out for the weight grad; dres (BN2) gets dz
 struct BnBack {
     const float *O, *Y, *mean, *stdv, *gamma, *dgamma, *dbeta, *nglob;
-    float *dy, *dres, *bsum;
+    float *dy, *dres;
     int R;
     const float* beta;   // ORC & 1: O's sign recomputed from Y (no residual)
 };
@@ -1299,7 +1300,6 @@ conv_wino_train_kernel(const float* __restrict__ X, const uint4* __restrict__ U,
             float4 be = make_float4(0.f, 0.f, 0.f, 0.f);
             if constexpr ((ORC & 1) != 0) be = reinterpret_cast<const float4*>(bb.beta)[cq];
             const size_t o0 = row0 * (F / 4);
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int k = 0; k < 8; k++) {
                 const size_t c = o0 + tid + 512 * k;
@@ -1321,25 +1321,11 @@ conv_wino_train_kernel(const float* __restrict__ X, const uint4* __restrict__ U,
                 reinterpret_cast<float4*>(bb.dy)[c] = d4;
                 if (bb.dres) reinterpret_cast<float4*>(bb.dres)[c] = dz;
                 act[(tid + 512 * k) / (F / 4) * RS + cq] = __builtin_bit_cast(uint4, d4);
-                acc.x += d4.x; acc.y += d4.y; acc.z += d4.z; acc.w += d4.w;
-            }
-            // the board's bias partial: the 8 row phases of each channel quad, in order, through the
-            // (not yet written) V buffers
-            float4* red = reinterpret_cast<float4*>(lds + PAD + XSZ + PAD);
-            red[tid] = acc;
-            __syncthreads();
-            if (tid < 64) {
-                float4 a = red[tid];
-                for (int k = 1; k < 8; k++) {
-                    const float4 q = red[64 * k + tid];
-                    a.x += q.x; a.y += q.y; a.z += q.z; a.w += q.w;
-                }
-                reinterpret_cast<float4*>(bb.bsum + (size_t)vgpr_index(bid) * 2 * F)[tid] = a;   // [board][2][F]
             }
         } else {
             for (int c = tid; c < 64 * (F / 4); c += 512) act[(c / (F / 4)) * RS + c % (F / 4)] = X4[c];
         }
-        __syncthreads();   // (XIN 2: also orders the bias partial's reads of V before wino_core writes V)
+        __syncthreads();
         wino_stamp(tr, 1);
         f32x4 y[NN][4];
         wino_core<F>(reinterpret_cast<char*>(act), (XSZ + PAD) * 16, rW, rW, bias, wr, w, lane, y);
@@ -1528,24 +1514,6 @@ struct HalfXf {
     }
 };
 
-// XIN 2: the board's sum of dy over its squares for the 16 channels of the chunk in slot s, in
-// conv_wino_train_kernel's order (row phases r = 0..7 each over squares r + 8 j, then the phases in
-// order); one wave, lane = channel + 16 x phase (r and r + 4)
-__device__ __forceinline__ void half_bsum(const char* l, int s, int lane, float* dst) {
-    const int ch = lane & 15, r4 = lane >> 4;
-    const float* p = reinterpret_cast<const float*>(l + hk::slot_off(s)) + ch;
-    float lo = 0.0f, hi = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        lo += p[(r4 + 8 * j) * hk::RS * 4];
-        hi += p[(r4 + 4 + 8 * j) * hk::RS * 4];
-    }
-    float a = lo;
-#pragma unroll
-    for (int r = 1; r < 8; r++) a += r < 4 ? __shfl(lo, ch + 16 * r, 64) : __shfl(hi, ch + 16 * (r - 4), 64);
-    if (lane < 16) dst[ch] = a;
-}
-
 // NP = 2 (halves) or 4 (quarters: 256 workgroups at 64 boards, one wave per SIMD of 16 output
 // channels, two steps' MFMAs interleaved so that two independent accumulator chains hide the f32
 // MFMA's dependent latency; every accumulator still takes its MFMAs in the same order)
@@ -1623,12 +1591,10 @@ conv_wino_part_kernel(const float* __restrict__ X, const uint4* __restrict__ U, 
             wr[i][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rW, voff + n * 1024, i * 16 * 1024, 0));
     __syncthreads();
     const HalfXf xf{l, w, lane};
-    float* const bsd = XIN == 2 ? bb.bsum + (size_t)board * 2 * F : nullptr;
     {
         f32x2 d0[4][2];
         xf.load(0, d0);
         xf.store(0, d0);
-        if (XIN == 2 && part == 0 && w == 0) half_bsum(l, 0, lane, bsd);
     }
     __syncthreads();
     wino_stamp(tr, 1);
@@ -1686,10 +1652,7 @@ conv_wino_part_kernel(const float* __restrict__ X, const uint4* __restrict__ U, 
                 if (st == 0 && stg) sg.issue(X, bn, bb, row0, tid, c + 2);
 #endif
                 if (st == 0 && more) xf.load((c + 1) & 1, dn);
-                if (st == TSPLIT && more) {
-                    xf.store((c + 1) & 1, dn);
-                    if (XIN == 2 && (c + 1) % NP == part && w == 0) half_bsum(l, (c + 1) & 1, lane, bsd + (c + 1) * CH);
-                }
+                if (st == TSPLIT && more) xf.store((c + 1) & 1, dn);
                 if (st == SPX - 1 && stg) sg.finish(l, bn, bb, invR, tid, c + 2, c & 1, (c + 2) % NP == part);
 #if AZ_HALF_ISSUE == 1
                 // the next staging's loads in flight across the barrier and the next chunk
@@ -2014,8 +1977,6 @@ struct Trainer {
     // reduction scratch
     float *wpart = nullptr, *cpart = nullptr, *dwtmp = nullptr;
     float* bpart = nullptr;                  // per-board BN partials [Bmax][2][F] (tr::BoardStats)
-    float* bsum = nullptr;                   // conv bias-grad partials of bn_back4_kernel [grid][2][C]
-    size_t bsum_cap = 0;
     size_t wpart_cap = 0, dwtmp_cap = 0;
     int slot = 0;                            // per-BN statistics stride (>= every BN's channels)
     float *tpol = nullptr, *tval = nullptr, *planes = nullptr, *loss = nullptr, *vpart = nullptr;
@@ -2028,6 +1989,8 @@ struct Trainer {
     std::vector<float> host_buf;
     int rank = 0, world = 1;
     uint32_t* stat_idx = nullptr; float* stat_buf = nullptr; int nstat = 0;
+    uint4* bias_tab = nullptr;               // bn_bias_grad_batched_kernel: one entry per BN-fed conv
+    int nbias = 0, bias_cmax = 0;
     // sharded batch (az_trainer_set_sharded): BatchNorm statistics, the BN backward sums and the
     // loss normalisation over every rank's rows; xfwd [world][2 slot + 1] forward exchange,
     // xback [2 slot] backward exchange, nglob the global row count (device), lossx the losses
@@ -2057,12 +2020,6 @@ struct Trainer {
     int wgrad_rows = 0;                      // A/B: a fixed weight-grad split size in rows (env AZ_TRAIN_WGRAD_ROWS)
     int wgrad_cosplit4 = 64;                 // ... and up to this many over four (env AZ_TRAIN_WGRAD_COSPLIT4; round 6: -0.9 %
                                              // at 64 against two, +1.5 % at 128)
-    // the conv bias gradients of the tower's BatchNorms: bn_back4 partials per BN, summed in one
-    // launch at the end of the backward (bias_dst[j] = gradient offset of BN j's conv bias)
-    float* bsum_all = nullptr;
-    size_t bsum_stride = 0;
-    uint32_t* bias_dst = nullptr;
-    std::vector<int> bias_pending;           // per BN: 0, or the partial blocks to sum
     std::vector<void*> allocs;
     // timing (HIP events on the trainer stream): whole steps and the gradient all-reduce
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -2462,7 +2419,7 @@ tr::BnIn bn_in(Trainer* T, int bi, size_t bn_off, const float* res, float* out) 
 
 // BN backward: dout (grad of the ReLU output O), pre-BN Y -> dy; dgamma/dbeta into the grad buffer
 // bpart: per-board dz / dz*yhat sums from the conv that produced dout (tr::BoardStats, STATS 2)
-// bias: the producing conv's bias gradient (sum of dy over rows), fused into the BN backward
+// bias: the producing conv's bias gradient (bn_bias_grad_kernel)
 int bias_grad(Trainer* T, const float* dy, int ld, int C, int R, float* dst);
 // the BN backward's sums: dgamma / dbeta of this rank into the gradient (from the producing conv's
 // per-board partials, or column sums), then -- sharded -- their global sums through xback;
@@ -2501,20 +2458,29 @@ int bn_back_sums(Trainer* T, int bi, const float* dout, const float* O, const fl
 }
 
 // the BN backward of BN bi staged in the next Winograd data-grad conv (tr::BnBack): its sums here,
-// the element-wise part in the conv's staging; bias partials per board, summed at the end
+// the element-wise part in the conv's staging; bias: the producing conv's bias gradient
+int bn_bias_grad(Trainer* T, int bi, int C, int R, size_t bn_off, const float* ub, float* bias);
 int bn_back_fused(Trainer* T, int bi, const float* dout, const float* O, const float* Y, int R, size_t bn_off,
-                  const float* bpart, float* dy, float* dres, tr::BnBack* bb) {
-    const int C = T->F, B = R / 64;
+                  const float* bpart, float* dy, float* dres, float* bias, tr::BnBack* bb) {
+    const int C = T->F;
     const float *ug, *ub;
     TRY(bn_back_sums(T, bi, dout, O, Y, C, C, R, bn_off, bpart, &ug, &ub));
-    if ((size_t)B * 2 * C > T->bsum_stride || bi >= (int)T->bias_pending.size()) return fail("bn: fused backward: bad shape");
+    TRY(bn_bias_grad(T, bi, C, R, bn_off, ub, bias));
     // BN 0 and the BN1s have no residual: the staging recomputes O's sign from Y (tr ORC bit 0)
     const bool orc = T->orc && (bi == 0 || bi % 2 == 1);
     *bb = tr::BnBack{O, Y, T->bmean + (size_t)bi * T->slot, T->bstd + (size_t)bi * T->slot, T->p + bn_off, ug, ub,
-                     T->sharded ? T->nglob : nullptr, dy, dres, T->bsum_all + (size_t)bi * T->bsum_stride, R,
-                     orc ? T->p + bn_off + C : nullptr};
-    T->bias_pending[bi] = B;     // partials per board
+                     T->sharded ? T->nglob : nullptr, dy, dres, R, orc ? T->p + bn_off + C : nullptr};
     return 0;
+}
+
+// dbeta of this rank is in the gradient (bn_back_sums); ub: the sum the backward uses (all ranks' when
+// sharded, and gone after this BatchNorm: written here; a rank-local batch writes them all at the end
+// of trainer_grads, bn_bias_grad_batched_kernel)
+int bn_bias_grad(Trainer* T, int bi, int C, int R, size_t bn_off, const float* ub, float* bias) {
+    if (!T->sharded) return 0;
+    tr::bn_bias_grad_kernel<<<(C + 255) / 256, 256, 0, T->st>>>(T->p + bn_off, T->bstd + (size_t)bi * T->slot, T->g + bn_off + C, ub,
+                                                                  T->sharded ? T->nglob : nullptr, R, C, bias);
+    return hipGetLastError() == hipSuccess ? 0 : fail("bn bias grad failed");
 }
 
 int bn_back_apply(Trainer* T, int bi, const float* dout, const float* O, const float* Y, int ld, int C, int R,
@@ -2528,7 +2494,7 @@ int bn_backward(Trainer* T, int bi, const float* dout, const float* O, const flo
 
 // sharded: the two head BatchNorms' backward sums share ONE exchange (xback = [dbeta_p 32 |
 // dgamma_p 32 | dbeta_v 8 | dgamma_v 8], every piece 16-byte aligned as in bn_back_sums)
-int bn_backward_heads_sharded(Trainer* T, int bi, int R, size_t poff, size_t voff) {
+int bn_backward_heads_sharded(Trainer* T, int bi, int R, size_t poff, size_t voff, float* pbias, float* vbias) {
     const float *ug, *ub;
     TRY(bn_back_sums(T, bi, T->da40, T->a40, T->y40, 64, 32, R, poff, nullptr, &ug, &ub, false));
     TRY(bn_back_sums(T, bi + 1, T->da40 + 32, T->a40 + 32, T->y40 + 32, 64, 8, R, voff, nullptr, &ug, &ub, false));
@@ -2538,13 +2504,13 @@ int bn_backward_heads_sharded(Trainer* T, int bi, int R, size_t poff, size_t vof
     for (int k = 0; k < 4; k++)
         AZ_HIP(hipMemcpyAsync(my + pos[k], T->g + off[k], cnt[k] * sizeof(float), hipMemcpyDeviceToDevice, T->st));
     TRY(sum_over_ranks(T, 80, "head BatchNorm backward sums"));
-    TRY(bn_back_apply(T, bi, T->da40, T->a40, T->y40, 64, 32, R, poff, T->dy40, nullptr, nullptr, T->xsum + 32,
+    TRY(bn_back_apply(T, bi, T->da40, T->a40, T->y40, 64, 32, R, poff, T->dy40, nullptr, pbias, T->xsum + 32,
                       T->xsum));
     return bn_back_apply(T, bi + 1, T->da40 + 32, T->a40 + 32, T->y40 + 32, 64, 8, R, voff, T->dy40 + 32, nullptr,
-                         nullptr, T->xsum + 72, T->xsum + 64);
+                         vbias, T->xsum + 72, T->xsum + 64);
 }
 
-// the element-wise BN backward with the sums ug (dgamma) / ub (dbeta): dy (+ dres), bias partials
+// the element-wise BN backward with the sums ug (dgamma) / ub (dbeta): dy (+ dres), the conv's bias gradient
 int bn_back_apply(Trainer* T, int bi, const float* dout, const float* O, const float* Y, int ld, int C, int R,
                   size_t bn_off, float* dy, float* dres, float* bias, const float* ug, const float* ub) {
     const float* mean = T->bmean + (size_t)bi * T->slot;
@@ -2553,20 +2519,13 @@ int bn_back_apply(Trainer* T, int bi, const float* dout, const float* O, const f
     float* dbet = T->g + bn_off + C;
     const float* nglob = T->sharded ? T->nglob : nullptr;
     if (bn_vec(C, ld, {dout, O, Y, dy, dres, T->p + bn_off, dgam, dbet, ug, ub, mean, sd})) {
-        const unsigned g = bn_grid(C, R);
-        if (bias && (size_t)g * 2 * C > T->bsum_cap) return fail("bn: bias partial buffer too small");
-        // the tower's conv biases: partials kept per BN, summed at the end of the backward in one launch
-        const bool batched = bias && T->bsum_all && bi < (int)T->bias_pending.size() && C == T->F;
-        float* bs = batched ? T->bsum_all + (size_t)bi * T->bsum_stride : T->bsum;
-        tr::bn_back4_kernel<<<g, 256, 0, T->st>>>(dout, O, Y, ld, C, R, mean, sd, T->p + bn_off, ug, ub, dy, dres,
-                                                  bias ? bs : nullptr, nglob);
-        if (batched) T->bias_pending[bi] = (int)g;
-        else if (bias) tr::finalize_sum_kernel<<<tr::finalize_grid(C), tr::FIN_THREADS, 0, T->st>>>(T->bsum, (int)g, C, bias);
+        tr::bn_back4_kernel<<<bn_grid(C, R), 256, 0, T->st>>>(dout, O, Y, ld, C, R, mean, sd, T->p + bn_off, ug, ub, dy, dres,
+                                                              nglob);
     } else {
         tr::bn_back_kernel<<<grid_for((size_t)R * C), 256, 0, T->st>>>(dout, O, Y, ld, C, R, mean, sd, T->p + bn_off,
                                                                        ug, ub, dy, dres, nglob);
-        if (bias && bias_grad(T, dy, ld, C, R, bias) != 0) return -1;
     }
+    if (bias) TRY(bn_bias_grad(T, bi, C, R, bn_off, ub, bias));
     return hipGetLastError() == hipSuccess ? 0 : fail("bn backward failed");
 }
 
@@ -2588,7 +2547,6 @@ int trainer_grads(Trainer* T, const float* planes, const float* tpol, const floa
     // anything below allocates or launches
     AZ_HIP(hipSetDevice(T->device));
     if (T->sharded && sharded_buffers(T)) return -1;
-    std::fill(T->bias_pending.begin(), T->bias_pending.end(), 0);
     AZ_HIP(hipEventRecord(T->ev[0], T->st));
     const int F = T->F, R = B * 64;
     hipStream_t st = T->st;
@@ -2695,10 +2653,11 @@ int trainer_grads(Trainer* T, const float* planes, const float* tpol, const floa
     // head BatchNorms -> dy40 (cols >= 40 stay zero)
     AZ_HIP(hipMemsetAsync(T->dy40, 0, (size_t)R * 64 * sizeof(float), st));
     if (T->sharded) {
-        TRY(bn_backward_heads_sharded(T, nbn, R, L.pbn, L.vbn));
+        TRY(bn_backward_heads_sharded(T, nbn, R, L.pbn, L.vbn, T->g + L.p1b, T->g + L.vb));
     } else {
-        TRY(bn_backward(T, nbn, T->da40, T->a40, T->y40, 64, 32, R, L.pbn, T->dy40, nullptr));
-        TRY(bn_backward(T, nbn + 1, T->da40 + 32, T->a40 + 32, T->y40 + 32, 64, 8, R, L.vbn, T->dy40 + 32, nullptr));
+        TRY(bn_backward(T, nbn, T->da40, T->a40, T->y40, 64, 32, R, L.pbn, T->dy40, nullptr, nullptr, T->g + L.p1b));
+        TRY(bn_backward(T, nbn + 1, T->da40 + 32, T->a40 + 32, T->y40 + 32, 64, 8, R, L.vbn, T->dy40 + 32, nullptr, nullptr,
+                        T->g + L.vb));
     }
     // heads 1x1: dW[F][64] -> policy_conv_1 [32][F], value_conv [8][F]
     TRY(launch_wgrad(T, 1, body, F, F, T->dy40, 64, 64, R, T->dwtmp, (size_t)F * 64));
@@ -2706,8 +2665,6 @@ int trainer_grads(Trainer* T, const float* planes, const float* tpol, const floa
     AZ_HIP(hipMemcpyAsync(T->g + L.p1w, T->dwtmp + (size_t)F * 64, (size_t)32 * F * sizeof(float), hipMemcpyDeviceToDevice, st));
     AZ_HIP(hipMemcpyAsync(T->g + L.vw, T->dwtmp + (size_t)F * 64 + (size_t)32 * F, (size_t)8 * F * sizeof(float),
                           hipMemcpyDeviceToDevice, st));
-    TRY(bias_grad(T, T->dy40, 64, 32, R, T->g + L.p1b));
-    TRY(bias_grad(T, T->dy40 + 32, 64, 8, R, T->g + L.vb));
     TRY(launch_conv(T, 1, T->dy40, 64, 64, T->w40d, F, nullptr, nullptr, T->dx, F, R));
     // residual tower, last block first
     // dout of every BN but the last block's second comes from a Winograd data-grad conv, whose
@@ -2727,16 +2684,16 @@ int trainer_grads(Trainer* T, const float* planes, const float* tpol, const floa
         };
         if (fuseb) {
             // BN2's backward (dout = dx) in conv2's data grad: dy (read by conv2's weight grad
-            // after it), dz (-> dres), bias partials; conv2's output dh with BN1's sums in bpart
+            // after it), dz (-> dres); conv2's output dh with BN1's sums in bpart
             tr::BnBack bb2;
             TRY(bn_back_fused(T, 2 + 2 * b, T->dx, T->xs[b + 1], T->y2[b], R, c2.bn, dx_stats ? T->bpart : nullptr, dy,
-                              T->dres, &bb2));
+                              T->dres, T->g + c2.b, &bb2));
             TRY(launch_wino(T, T->dx, T->ud[2 + 2 * b], nullptr, nullptr, T->dh, B, 2, bstat(1 + 2 * b, T->hh[b], T->y1[b]),
                             {}, bb2));
             TRY(launch_wino_wgrad(T, T->hh[b], dy, B, T->g + c2.w));
             // BN1's backward (dout = dh) in conv1's data grad (+ dres): dy, output dxn
             tr::BnBack bb1;
-            TRY(bn_back_fused(T, 1 + 2 * b, T->dh, T->hh[b], T->y1[b], R, c1.bn, T->bpart, dy, nullptr, &bb1));
+            TRY(bn_back_fused(T, 1 + 2 * b, T->dh, T->hh[b], T->y1[b], R, c1.bn, T->bpart, dy, nullptr, T->g + c1.b, &bb1));
             TRY(launch_wino(T, T->dh, T->ud[1 + 2 * b], nullptr, T->dres, T->dxn, B, 2,
                             bstat(2 * b, T->xs[b], b > 0 ? T->y2[b - 1] : T->y0), {}, bb1));
             TRY(launch_wino_wgrad(T, T->xs[b], dy, B, T->g + c1.w));
@@ -2776,20 +2733,9 @@ int trainer_grads(Trainer* T, const float* planes, const float* tpol, const floa
                     T->g + L.tower[0].b));
     TRY(launch_wgrad(T, 9, T->x0, tr::X0C, tr::X0C, T->dy, F, F, R, T->dwtmp, T->dwtmp_cap));
     tr::unpack3x3_kernel<<<grid_for((size_t)9 * 19 * F), 256, 0, st>>>(T->dwtmp, F, 19, tr::X0C, T->g + L.tower[0].w);
-    if (!T->bias_pending.empty()) {   // the tower's conv bias gradients: one launch for BNs 1..2B
-        const int nt = (int)T->bias_pending.size();
-        bool same = nt > 1;
-        for (int j = 1; j < nt; j++) same = same && T->bias_pending[j] == T->bias_pending[1];
-        const int j0 = same ? 1 : 0;
-        if (same && T->bias_pending[1] > 0)
-            tr::finalize_sum_batched_kernel<<<dim3(tr::finalize_grid(F), nt - 1), tr::FIN_THREADS, 0, st>>>(
-                T->bsum_all + T->bsum_stride, T->bsum_stride, T->bias_pending[1], F, T->bias_dst + 1, T->g);
-        for (int j = same ? 0 : j0; j < (same ? 1 : nt); j++)
-            if (T->bias_pending[j] > 0)
-                tr::finalize_sum_kernel<<<tr::finalize_grid(F), tr::FIN_THREADS, 0, st>>>(
-                    T->bsum_all + (size_t)j * T->bsum_stride, T->bias_pending[j], F, T->g + L.tower[j].b);
-        std::fill(T->bias_pending.begin(), T->bias_pending.end(), 0);
-    }
+    if (!T->sharded)   // the BN-fed conv bias gradients of a rank-local batch
+        tr::bn_bias_grad_batched_kernel<<<dim3((T->bias_cmax + 255) / 256, T->nbias), 256, 0, st>>>(T->p, T->bstd, T->slot, T->g,
+                                                                                              T->bias_tab, R);
     AZ_HIP(hipMemcpyAsync(T->hloss, T->loss, (size_t)B * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
     AZ_HIP(hipStreamSynchronize(st));
     double pl = 0.0, vl = 0.0;
@@ -2963,15 +2909,6 @@ int az_trainer_create(int blocks, int filters, const float* weights, size_t n, i
     T->wpart = A(wp);
     T->cpart = A((R / tr::CS_ROWS + 2) * 2 * (size_t)std::max(F, 65));
     T->bpart = A((size_t)max_batch * 2 * F);
-    T->bsum_cap = (size_t)256 * 4 * 2 * std::max(F, 64);   // bn_grid's workgroup cap x [2][C]
-    T->bsum = A(T->bsum_cap);
-    if (T->wino) {   // per-BN bias partials of the tower (batched finalize) and the second dy
-        // a slot holds either bn_back4's per-workgroup partials or the fused backward's per-board
-        // ones (B x [2][F]): the larger of the two at max_batch
-        T->bsum_stride = std::max(T->bsum_cap, (size_t)max_batch * 2 * F);
-        T->bsum_all = A((size_t)nconv * T->bsum_stride);
-        T->bias_pending.assign(nconv, 0);
-    }
     // dW scratch: input conv [9][64][F], residual conv [9][F][F], heads [F][64] + its [40][F]
     // transpose, policy_conv_2 [32][64], value_linear_2 partial sums (65)
     T->dwtmp_cap = std::max({(size_t)9 * 64 * F, (size_t)9 * F * F, (size_t)F * 64 + 40 * (size_t)F, (size_t)32 * 64,
@@ -2998,18 +2935,20 @@ int az_trainer_create(int blocks, int filters, const float* weights, size_t n, i
     bn_stats(T->L.pbn, 32);
     bn_stats(T->L.vbn, 8);
     T->nstat = (int)sidx.size();
-    if (T->wino) {
-        std::vector<uint32_t> bd;
-        for (const auto& c : T->L.tower) bd.push_back((uint32_t)c.b);
-        T->bias_dst = reinterpret_cast<uint32_t*>(T->alloc(bd.size()));
-        if (!T->bias_dst || hipMemcpy(T->bias_dst, bd.data(), bd.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            delete T;
-            return fail("az_trainer_create: out of device memory");
-        }
-    }
     T->stat_idx = reinterpret_cast<uint32_t*>(T->alloc(sidx.size()));
     T->stat_buf = T->alloc(sidx.size());
-    if (!T->stat_idx || !T->stat_buf) { delete T; return fail("az_trainer_create: out of device memory"); }
+    std::vector<uint4> btab;                 // BN index: the tower's in order, then policy, value
+    for (const auto& c : T->L.tower) btab.push_back(uint4{(uint32_t)c.bn, (uint32_t)c.b, (uint32_t)c.cout, (uint32_t)btab.size()});
+    btab.push_back(uint4{(uint32_t)T->L.pbn, (uint32_t)T->L.p1b, 32u, (uint32_t)btab.size()});
+    btab.push_back(uint4{(uint32_t)T->L.vbn, (uint32_t)T->L.vb, 8u, (uint32_t)btab.size()});
+    T->nbias = (int)btab.size();
+    T->bias_cmax = std::max(F, 32);
+    T->bias_tab = reinterpret_cast<uint4*>(T->alloc(btab.size() * 4));
+    if (!T->stat_idx || !T->stat_buf || !T->bias_tab ||
+        hipMemcpy(T->bias_tab, btab.data(), btab.size() * sizeof(uint4), hipMemcpyHostToDevice) != hipSuccess) {
+        delete T;
+        return fail("az_trainer_create: out of device memory");
+    }
     if (hipMemcpy(T->p, weights, T->np * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(T->mask, mask.data(), T->np, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(T->stat_idx, sidx.data(), sidx.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||

@@ -89,18 +89,27 @@ class TrainRef:
     def _conv(self, x, name, pad):
         return Fn.conv2d(x, self.P[name + ".weight"], self.P[name + ".bias"], padding=pad)
 
-    def forward(self, planes, masks=None):
+    def forward(self, planes, masks=None, record=None):
         """masks (optional): ReLU masks in forward order (input block, then per residual block
         the inner and the outer ReLU, heads [B,40,8,8] policy|value, value hidden [B,64]) --
         given, every ReLU multiplies by that mask instead of testing its own sign, so a
-        pre-activation within rounding of 0 takes the same branch as in the run that made them."""
+        pre-activation within rounding of 0 takes the same branch as in the run that made them.
+        record (optional): a list that receives the masks this run used (output > 0, or the given
+        masks), as bool arrays in the order and shapes that masks= accepts."""
         M = None if masks is None else [torch.tensor(np.asarray(m), dtype=self.dtype) for m in masks]
+        rec = {}
 
         def relu(z, k, sl=None):
             if M is None:
-                return torch.relu(z)
-            m = M[k] if sl is None else M[k][:, sl]
-            return z * m
+                m = z.detach() > 0
+                y = torch.relu(z)
+            else:
+                m = (M[k] if sl is None else M[k][:, sl])
+                y = z * m
+                m = m != 0
+            if record is not None:
+                rec.setdefault(k, []).append(m.numpy().copy())
+            return y
 
         x = torch.tensor(np.asarray(planes, np.float32).reshape(-1, 19, 8, 8), dtype=self.dtype)
         x = relu(self._bn(self._conv(x, "input_conv", 1), "input_bn"), 0)
@@ -116,14 +125,16 @@ class TrainRef:
         v = relu(self._bn(self._conv(x, "value_conv", 0), "value_bn"), nh, slice(32, 40)).reshape(x.shape[0], -1)
         v = relu(v @ self.P["value_linear_1.weight"] + self.P["value_linear_1.bias"], nh + 1)
         value = torch.tanh(v @ self.P["value_linear_2.weight"] + self.P["value_linear_2.bias"]).squeeze(1)
+        if record is not None:      # the two head ReLUs share slot nh: policy | value along the channels
+            record[:] = [np.concatenate(rec[k], axis=1) for k in range(nh + 2)]
         return policy, value
 
-    def grads(self, planes, tpol, tval, masks=None):
+    def grads(self, planes, tpol, tval, masks=None, record=None):
         """Returns (flat gradient float64 array, (policy_loss, value_loss)) and leaves the updated
-        running statistics in self.stats."""
+        running statistics in self.stats.  record: as in forward."""
         for t in self.P.values():
             t.grad = None
-        policy, value = self.forward(planes, masks)
+        policy, value = self.forward(planes, masks, record)
         t = torch.tensor(np.asarray(tpol, np.float32), dtype=self.dtype)
         z = torch.tensor(np.asarray(tval, np.float32), dtype=self.dtype)
         pl = -(t * torch.log(policy + 1e-5)).sum(dim=1).mean()

@@ -92,17 +92,24 @@ def test_grads_losses_and_running_stats_match_oracle(require_gpu, blocks, filter
 
 
 def test_adamw_and_clipping_bit_exact(require_gpu):
-    blocks, filters = 2, 32
-    w = A.random_weights(blocks, filters, seed=3)
-    tr = A.Trainer(blocks, filters, weights=w, max_batch=16)
+    """Three AdamW steps bit-exact against the float32 restatement, on gamma5+peaked(8,4) weights
+    and hard targets (tests/traincases.py CLIP), where the value clip clamps: at every step the
+    GPU gradient has >= 100 entries beyond +-1, of both signs, and more than half inside
+    (tests/test_traincases.py test_clipping_case_clamps holds the same on the float64 oracle)."""
+    import traincases as C
+    blocks, filters, n = C.CLIP["blocks"], C.CLIP["filters"], C.CLIP["n"]
+    w = C.family_weights(C.CLIP["family"], A.random_weights(blocks, filters, seed=C.CLIP["wseed"]), blocks, filters)
+    tr = A.Trainer(blocks, filters, weights=w, max_batch=n)
     mask = T.trainable_mask(blocks, filters)
     m = np.zeros_like(w)
     v = np.zeros_like(w)
     p = tr.params()
-    for step, it in enumerate([5, 13, 1002]):
-        planes, tpol, tval = batch(16, seed=step)
+    for step, it in enumerate(C.CLIP["its"]):
+        planes, tpol, tval = C.hard_targets(batch(n, seed=C.CLIP["batch_seeds"][step]), blocks, filters, w)
         tr.compute_gradients(planes, tpol, tval)
         g = tr.grads()
+        print("step %d: |g| > 1: %d (+%d / -%d), |g| < 1: %d of %d" % ((step,) + C.clip_counts(g)))
+        C.assert_clip_engages(g)            # clipping engaged
         p = tr.params()                     # running statistics moved during the forward
         lr = A.get_cyclical_lr(it)
         assert lr == T.cyclical_lr(it)
@@ -110,8 +117,6 @@ def test_adamw_and_clipping_bit_exact(require_gpu):
         p, m, v = T.adamw_step(p, g, m, v, mask, step + 1, lr)
         got = tr.params()
         assert np.array_equal(got, p), np.abs(got - p).max()
-    # clipping engaged: some gradient entries exceed 1 in magnitude on this batch
-    assert np.abs(g).max() > 0
 
 
 def test_step_is_deterministic_and_comm_world1_is_identity(require_gpu):
@@ -270,8 +275,8 @@ def test_bn_staging_matches_separate_bn_kernels(require_gpu, monkeypatch, blocks
     step with separate BN kernels (AZ_TRAIN_FUSE_BN=0: bn_apply4 / bn_back4 and the convs' plain
     staging): the staging does their arithmetic element for element and both take the statistics
     from the convs' per-board partials, so losses, running statistics and every gradient but the
-    BN-fed conv biases are bit-identical (those biases' exact gradient is 0: their partial sums
-    are added in another order, |g| <= 1e-5 either way).  n = 300 boards: the persistent convs'
+    BN-fed conv biases are bit-identical (those biases' exact gradient is 0: |g| <= 1e-5 either
+    way).  n = 300 boards: the persistent convs'
     256 workgroups take two boards each for 44 of them; n = 13: fewer boards than workgroups."""
     w = A.random_weights(blocks, 256, seed=23)
     planes, tpol, tval = batch(n, seed=400 + n)
@@ -418,12 +423,16 @@ def test_data_parallel_world2_bit_exact(require_gpu):
     the same float32 sum in either order), then AdamW with world = 2 (gradient scale 1/2 before the
     clip) and the BatchNorm running statistics averaged.  Both ranks end bit-identical, and equal
     to the float32 restatement T.adamw_step(p, g0 + g1, ..., world=2) with averaged statistics.
+    On gamma5+peaked(8,4) weights and hard targets (tests/traincases.py WORLD2), so that the summed
+    gradient has entries in (1, 2] -- which clip(g / 2) leaves alone and clip(g) / 2 would clamp --
+    and above 2.
     Note the reference trains one batch of 512 on one device (training.rs:138): with 512 per rank
     the global batch is 512 x world and BatchNorm sees per-rank statistics."""
     import threading
-    blocks, filters, n = 2, 64, 16
-    w = A.random_weights(blocks, filters, seed=21)
-    planes, tpol, tval = batch(2 * n, seed=22)
+    import traincases as C
+    blocks, filters, n = C.WORLD2["blocks"], C.WORLD2["filters"], C.WORLD2["n"]
+    w = C.family_weights(C.WORLD2["family"], A.random_weights(blocks, filters, seed=C.WORLD2["wseed"]), blocks, filters)
+    planes, tpol, tval = C.hard_targets(batch(2 * n, seed=C.WORLD2["batch_seed"]), blocks, filters, w)
     ranks = [A.Trainer(blocks, filters, weights=w, max_batch=n) for _ in range(2)]
     slots, bar = [None, None], threading.Barrier(2, timeout=30)
 
@@ -441,7 +450,7 @@ def test_data_parallel_world2_bit_exact(require_gpu):
     m = np.zeros_like(w)
     v = np.zeros_like(w)
     want = w.copy()
-    for step, it in enumerate([3, 12]):
+    for step, it in enumerate(C.WORLD2["its"]):
         gs, ps = [], []
         for r, tr in enumerate(ranks):
             tr.compute_gradients(planes[r * n:(r + 1) * n], tpol[r * n:(r + 1) * n], tval[r * n:(r + 1) * n])
@@ -456,6 +465,9 @@ def test_data_parallel_world2_bit_exact(require_gpu):
             t.join(timeout=120)
         assert errs == [None, None]
         assert np.array_equal(ps[0][mask], want[mask]) and np.array_equal(ps[1][mask], want[mask])
+        mid, high = C.world2_counts(gs[0] + gs[1])
+        print("step %d: |g0 + g1| in (1, 2]: %d, above 2: %d" % (step, mid, high))
+        assert mid >= 100 and high >= 100, (mid, high)
         want, m, v = T.adamw_step(want, gs[0] + gs[1], m, v, mask, step + 1, lr, world=2)
         stats = ~mask
         want[stats] = (ps[0][stats] + ps[1][stats]) * np.float32(0.5)
@@ -758,8 +770,8 @@ def test_train_loop_per_rank_opt_in_two_ranks(require_gpu):
 
 
 def test_winograd_trainer_more_than_1024_positions(require_gpu):
-    """the fused BN backward keeps per-board bias partials (B x [2][F]) in slots sized for
-    max_batch, so a Winograd trainer takes more than 1024 positions per step; its gradients equal
+    """the fused BN backward has no buffer sized for a fixed batch (it once kept per-board
+    bias partials), so a Winograd trainer takes more than 1024 positions per step; its gradients equal
     the unfused backward's (AZ_TRAIN_FUSE_BN=0) within 1e-5 relative norm."""
     import os
     w = A.random_weights(1, 256, seed=61)
