@@ -169,10 +169,30 @@ int az_search_set_roots_from(az_search* s, const az_pos* start, const int32_t* h
  * be NULL): improved policy [G,4096], visits [G,4096], max_subtree_depth [G]. */
 int az_search_run(az_search* s, float* improved, uint32_t* visits, int32_t* depth);
 /* The current roots' visits / improved policy / max_subtree_depth without running simulations:
- * the reference's public MCTree fields (tree.rs:25-34), e.g. mid-move during az_selfplay_run_sims. */
+ * the reference's public MCTree fields (tree.rs:25-34), e.g. mid-move during az_selfplay_run_sims:
+ * after k simulations of a move the outputs are exactly the tree after those k (every one backed
+ * up, none counted twice), and reading changes nothing.  A root that no simulation has visited
+ * yet (right after az_search_set_roots, az_search_advance or a completed self-play move) reads
+ * visits all 0 and depth 0; its improved policy is 0 / 0: NaN at the indices of the root's legal
+ * moves and 0 everywhere else (bench.py --dump-outputs reads the roots' legal moves off it). */
 int az_search_read_roots(az_search* s, float* improved, uint32_t* visits, int32_t* depth);
 /* traverse_new(action, apply_noise) for every game (tree.rs:239-256) after playing the
- * action on its GameState (training.rs:323-325).  result[g] receives the play_move result. */
+ * action on its GameState (training.rs:323-325).  result[g] receives the play_move result:
+ *   AZ_ONGOING: the game goes on.  Its root is now the action's child: the child's priors are kept,
+ *     its visits and scores are zeroed and every other node is dropped, so the next az_search_run
+ *     equals a fresh search of the extended history.  With apply_noise the new root gets Dirichlet
+ *     noise from the stream (seed, game_id, ply + 1, 0), ply being the noise ply of the root left
+ *     behind (az_search_set_roots' noise_ply; each advance adds one).
+ *   AZ_DRAW / AZ_WHITE_WINS / AZ_BLACK_WINS: the move ends the game (mate, stalemate, insufficient
+ *     material, threefold repetition, the 50-move or the 200-fullmove limit).
+ *   AZ_ILLEGAL: actions[g] is not the index of a legal move of the root (anything outside
+ *     0..4095 included), or it is a legal move that no simulation has expanded -- the engine keeps
+ *     no child to re-root on (the reference's traverse_new panics there); also the answer for a
+ *     game that was inactive already.
+ * Every game whose result is not AZ_ONGOING becomes inactive until the next az_search_set_roots:
+ * az_search_run runs no simulation for it (none is counted in az_search_stats), az_search_advance
+ * ignores its action, and az_search_run / az_search_read_roots keep returning the visits, improved
+ * policy and depth its root had when it went inactive. */
 int az_search_advance(az_search* s, const int32_t* actions, int apply_noise, int32_t* result);
 
 /* run_all_episodes (training.rs:340-378): reset all G slots to new games from startpos */

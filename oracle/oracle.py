@@ -79,6 +79,7 @@ def lib():
         L.ref_play_unchecked.argtypes = [P(RefPos), RefMove]
         L.ref_pos_bitboards.argtypes = [P(RefPos), P(C.c_uint64)]
         L.ref_game_new.argtypes = [P(RefGame)]
+        L.ref_game_from.argtypes = [P(RefGame), P(RefPos)]
         L.ref_game_free.argtypes = [P(RefGame)]
         L.ref_play_move.argtypes = [P(RefGame), RefMove]
         L.ref_splitmix64.argtypes = [C.c_uint64]
@@ -235,11 +236,15 @@ def random_playouts(seed, ngames, max_plies=400, cap=200000):
 
 
 class Game:
-    """GameState restatement (chess.rs:13-63)."""
+    """GameState restatement (chess.rs:13-63); `start` (a RefPos): a state whose repetition multiset
+    begins at that position instead of the startpos."""
 
-    def __init__(self):
+    def __init__(self, start=None):
         self._g = RefGame()
-        lib().ref_game_new(C.byref(self._g))
+        if start is None:
+            lib().ref_game_new(C.byref(self._g))
+        else:
+            lib().ref_game_from(C.byref(self._g), C.byref(start))
 
     def __del__(self):
         try:

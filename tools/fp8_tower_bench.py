@@ -14,7 +14,6 @@ sysfs around every round.
     python tools/fp8_tower_bench.py [--out profiles/fp8_tower_bench.txt]
 """
 import argparse
-import ctypes as C
 import glob
 import json
 import os
@@ -28,6 +27,7 @@ import numpy as np  # noqa: E402
 
 import azchess as A  # noqa: E402
 from azchess import _lib as L  # noqa: E402
+from azchess.hiprt import Hip  # noqa: E402
 
 PEAK_TFLOPS = {"fp8": 5000.0, "bf16": 2500.0}
 
@@ -42,53 +42,6 @@ def sclk_mhz():
         except (OSError, ValueError, IndexError):
             pass
     return None
-
-
-class Hip:
-    """the few calls of the HIP runtime libaz is bound to (device buffers, a stream, events)"""
-
-    def __init__(self):
-        paths = L.hip_runtime_paths()
-        if not paths:
-            raise SystemExit("fp8_tower_bench: libaz maps no HIP runtime")
-        self.rt = C.CDLL(paths[0])
-
-    def ck(self, rc):
-        if rc != 0:
-            raise RuntimeError("HIP error %d" % rc)
-
-    def malloc(self, nbytes):
-        p = C.c_void_p()
-        self.ck(self.rt.hipMalloc(C.byref(p), C.c_size_t(nbytes)))
-        return p
-
-    def upload(self, arr):
-        p = self.malloc(arr.nbytes)
-        self.ck(self.rt.hipMemcpy(p, arr.ctypes.data_as(C.c_void_p), C.c_size_t(arr.nbytes), 1))
-        return p
-
-    def download(self, p, arr):
-        self.ck(self.rt.hipMemcpy(arr.ctypes.data_as(C.c_void_p), p, C.c_size_t(arr.nbytes), 2))
-        return arr
-
-    def stream(self):
-        s = C.c_void_p()
-        self.ck(self.rt.hipStreamCreate(C.byref(s)))
-        return s
-
-    def event(self):
-        e = C.c_void_p()
-        self.ck(self.rt.hipEventCreate(C.byref(e)))
-        return e
-
-    def record(self, e, s):
-        self.ck(self.rt.hipEventRecord(e, s))
-
-    def elapsed_ms(self, e0, e1):
-        self.ck(self.rt.hipEventSynchronize(e1))
-        ms = C.c_float()
-        self.ck(self.rt.hipEventElapsedTime(C.byref(ms), e0, e1))
-        return float(ms.value)
 
 
 def tower_flop_per_row(blocks, filters):
