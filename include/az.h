@@ -136,7 +136,12 @@ typedef struct {
     int noise;          /* Dirichlet noise at roots (training.rs:358, tree.rs:243) */
     uint64_t seed;      /* counter-based RNG seed (replaces thread_rng) */
     int evaluator;      /* AZ_EVAL_NET, AZ_EVAL_SYNTHETIC or AZ_EVAL_CALLBACK */
-    int continuous;     /* self-play: restart a finished slot with a new game */
+    int continuous;     /* self-play: restart a finished slot with a new game.  Game ids: slots
+                           start with ids 0..games-1; new ids are handed out in finishing
+                           order, starting at `games`.  Games that end in the same step get
+                           consecutive ids in no defined slot order (it can differ from run to
+                           run).  A game's content (noise, move choice: the streams keyed by
+                           seed, game id, ply) depends on its id only, never on the slot. */
     int record_evals;   /* keep a log of every evaluation (for replay parity) */
     int eval_log_cap;   /* log capacity in rows */
     int cache_capacity; /* FEN evaluation cache entries (CACHE_CAPACITY, parameters.rs:4; 0 = off):
