@@ -18,6 +18,9 @@ MAX_MOVES = 256
 ONGOING, DRAW, WHITE_WINS, BLACK_WINS, ILLEGAL = 0, 1, 2, 3, -1
 DTYPE_F32, DTYPE_BF16, DTYPE_FP8 = 0, 1, 2
 EVAL_NET, EVAL_SYNTHETIC, EVAL_CALLBACK = 0, 1, 2
+# az_net_packed_read kinds (include/az.h AZ_PACKED_*), in enum order
+PACKED_KINDS = ("conv_w", "conv_b", "in_pk32", "wino_w", "wino16_w", "wino16_us", "w8", "w8s", "b8", "head",
+                "head_frag", "head_frag32")
 
 
 class AzPos(C.Structure):
@@ -106,6 +109,12 @@ SIGNATURES = [
     ("az_net_save_mpk", C.c_int, [C.c_char_p, C.c_int, C.c_int, P(C.c_float), C.c_size_t]),
     ("az_net_forward", C.c_int, [C.c_void_p, P(C.c_float), C.c_int, P(C.c_float), P(C.c_float)]),
     ("az_net_forward_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("az_net_update_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("az_net_update", C.c_int, [C.c_void_p, P(C.c_float), C.c_size_t]),
+    ("az_net_update_from_trainer", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("az_net_generation", C.c_int64, [C.c_void_p]),
+    ("az_net_get_weights", C.c_int, [C.c_void_p, P(C.c_float), C.c_size_t]),
+    ("az_net_packed_read", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     ("az_search_default_cfg", C.c_int, [P(AzSearchCfg)]),
     ("az_search_create", C.c_int, [C.c_void_p, P(AzSearchCfg), C.c_int, P(C.c_void_p)]),
     ("az_search_destroy", C.c_int, [C.c_void_p]),

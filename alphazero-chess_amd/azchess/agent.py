@@ -89,15 +89,57 @@ class AlphaZero:
             raise ValueError("dtype must be one of %s, not %r" % (", ".join(sorted(DTYPES)), dtype))
         if weights is None:
             weights = random_weights(blocks, filters, seed)
-        self.weights = np.ascontiguousarray(weights, np.float32)
+        self._weights = np.ascontiguousarray(weights, np.float32)
         self.blocks, self.filters = blocks, filters
         self.dtype = dtype
         desc = L.AzNetDesc(blocks, filters, DTYPES[dtype])
         h = C.c_void_p()
-        L.check(L.lib.az_net_create(C.byref(desc), L.fptr(self.weights), self.weights.size, device, C.byref(h)))
+        L.check(L.lib.az_net_create(C.byref(desc), L.fptr(self._weights), self._weights.size, device, C.byref(h)))
         self._h = h
         # libaz runs the fused tower kernel unless AZ_FUSED_TOWER=0 (an fp8 net has no other: creation fails)
         self.fused_tower = os.environ.get("AZ_FUSED_TOWER", "1") != "0"
+
+    @property
+    def weights(self):
+        """The flat f32 parameters this net evaluates: the creator's host copy, or after an update the
+        net's own device copy, read back on first use (az_net_get_weights)."""
+        if self._weights is None:
+            out = np.empty(num_params(self.blocks, self.filters), np.float32)
+            L.check(L.lib.az_net_get_weights(self._h, L.fptr(out), out.size))
+            self._weights = out
+        return self._weights
+
+    @property
+    def generation(self):
+        """0 after creation, + 1 for each update / update_from."""
+        return int(L.check(L.lib.az_net_generation(self._h)))
+
+    def update(self, weights):
+        """Replace the weights in place from host parameters (a checkpoint, an arena opponent): one
+        upload, then the BatchNorm fold and every packed layout rebuilt by kernels on the device
+        (az_net_update).  Searches on this net set their roots again (or reset) before they run."""
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        L.check(L.lib.az_net_update(self._h, L.fptr(w), w.size))
+        self._weights = None
+        return self
+
+    def update_from(self, trainer):
+        """model.valid() (training.rs:83): take the trainer's current device parameters, device to device
+        (az_net_update_from_trainer)."""
+        L.check(L.lib.az_net_update_from_trainer(self._h, trainer._h))
+        self._weights = None
+        return self
+
+    def packed(self, kind, index=0):
+        """Test hook (az_net_packed_read): the bytes of one packed weight buffer, kind one of
+        _lib.PACKED_KINDS; None for a buffer this net does not hold."""
+        k = L.PACKED_KINDS.index(kind)
+        n = L.check(L.lib.az_net_packed_read(self._h, k, int(index), None, 0))
+        if n == 0:
+            return None
+        out = np.empty(n, np.uint8)
+        L.check(L.lib.az_net_packed_read(self._h, k, int(index), out.ctypes.data_as(C.c_void_p), n))
+        return out
 
     @property
     def tower_kernel(self):

@@ -268,10 +268,16 @@ class Trainer:
         L.check(L.lib.az_trainer_exchange_stats(self._h, C.byref(a), C.byref(b), C.byref(c), int(reset)))
         return a.value, b.value, c.value
 
-    def model(self, dtype="f32"):
+    def model(self, dtype="f32", into=None):
         """model.valid() for self-play (training.rs:83): an inference net with the current weights,
-        f32 like the reference's Cuda<f32> backend (bf16 is an explicit throughput opt-in)."""
+        f32 like the reference's Cuda<f32> backend (bf16 is an explicit throughput opt-in).
+        into: an AlphaZero of this shape to refresh in place from the device parameters
+        (AlphaZero.update_from: nothing goes to the host, its buffers and searches stay) and return."""
         from .agent import AlphaZero
+        if into is not None:
+            if into.dtype != dtype:
+                raise ValueError("Trainer.model: into is a %s net, dtype=%r asked" % (into.dtype, dtype))
+            return into.update_from(self)
         return AlphaZero(self.blocks, self.filters, weights=self.params(), dtype=dtype, device=self.device)
 
 
@@ -342,9 +348,10 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
     trainer.set_sharded(shard_batch)   # a caller's trainer too (its comm / reducer is the caller's)
     replay = replay if replay is not None else ReplayBuffer()
     history = []
+    model = None
     for iteration in range(iterations):
         t0 = time.perf_counter()
-        model = trainer.model(dtype)
+        model = trainer.model(dtype, into=model)   # created once, then refreshed in place on the device
         new_unique, plays, sims_done, games_done, steps_done, moves_done, finished = 0, 0, 0, 0, 0, 0, 0
         steps_global = 0
         while True:

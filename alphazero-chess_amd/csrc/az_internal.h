@@ -200,6 +200,11 @@ struct NetDev {
     // scratch for az_net_forward
     void* x = nullptr; void* h = nullptr; void* planes = nullptr; int scratch_rows = 0;
     float* d_in = nullptr; float* d_pol = nullptr; float* d_val = nullptr; int io_rows = 0;
+    // in-place updates (net_update.hip): 0 after net_create, + 1 per update; the searches compare it with
+    // the generation their roots were set under.  upd: the device scratch of the update kernels (the flat
+    // parameters of the last update among it), allocated by the first update
+    int64_t generation = 0;
+    struct NetUpdate* upd = nullptr;
 };
 
 // offsets inside NetDev::head
@@ -235,6 +240,10 @@ struct SearchOut {
 
 int net_create(const az_net_desc* d, const float* w, size_t n, int device, NetDev** out);
 void net_destroy(NetDev* n);
+// net_update.hip: rewrite every weight buffer of n in place from the flat parameters d_w (device, n's
+// device), byte for byte what net_create builds from them; ordered after st, returns when done
+int net_update_device(NetDev* n, const float* d_w, size_t count, hipStream_t st);
+void net_update_free(NetDev* n);
 // planes [rows][64][32] in the net's dtype (device). count may be nullptr (all rows valid).
 // ev0/ev1 (optional) bracket the first residual conv launch (timing of one 3x3 FxF conv)
 int net_tower(NetDev* n, const void* planes, const int* count, int rows, void* x, void* h, hipStream_t st,

@@ -796,6 +796,7 @@ void net_destroy(NetDev* n) {
     (void)hipFree(n->w8); (void)hipFree(n->w8s); (void)hipFree(n->b8);
     (void)hipFree(n->x); (void)hipFree(n->h); (void)hipFree(n->planes);
     (void)hipFree(n->d_in); (void)hipFree(n->d_pol); (void)hipFree(n->d_val);
+    net_update_free(n);
     if (n->stream) (void)hipStreamDestroy(n->stream);
     delete n;
 }

@@ -505,6 +505,7 @@ struct az_search {
     size_t finished_read = 0;
     bool roots_fresh = false;        // trees sized for exactly S sims per root
     int sim_cursor = 0;              // simulation steps of the current self-play move already run
+    int64_t net_gen = 0;             // the net's generation (az_net_update*) when the roots were last set
     // timing
     bool timing = false;
     bool fused_steps = AZ_FUSED_STEPS != 0;   // k_step (backup + select + expand in one launch); env AZ_FUSED_STEPS=0: separate kernels
@@ -530,6 +531,21 @@ template <typename T> int dalloc(az_search* s, T** p, size_t count) {
     s->allocs.push_back(q);
     *p = (T*)q;
     return 0;
+}
+
+// In-place weight updates (net_update.hip).  Setting roots on a net whose generation has moved first
+// empties the FEN cache: nothing evaluated under the old weights may serve the new ones.
+int adopt_net_generation(az_search* s) {
+    if (!s->net || s->net->dev->generation == s->net_gen) return 0;
+    if (s->E.cache_mask >= 0) AZ_HIP(hipMemset(s->E.c_state, 0, (size_t)(s->E.cache_mask + 1) * sizeof(unsigned)));
+    s->net_gen = s->net->dev->generation;
+    return 0;
+}
+// ... and a search whose trees were built under the old weights does not go on: its priors would mix two nets
+int check_net_generation(const az_search* s, const char* who) {
+    if (!s->net || s->net->dev->generation == s->net_gen) return 0;
+    return fail(std::string(who) + ": the net's weights changed since this search's roots were set; set roots "
+                "(az_search_set_roots) or az_selfplay_reset first");
 }
 
 constexpr int EV_PER_STEP = 9;
@@ -882,6 +898,7 @@ int az_search_create(az_net* net, const az_search_cfg* cfg, int device, az_searc
     s->cfg = *cfg;
     s->device = device;
     s->net = net;
+    s->net_gen = net ? net->dev->generation : 0;
     if (const char* v = getenv("AZ_FUSED_STEPS")) s->fused_steps = atoi(v) != 0;   // A/B and parity tests
     if (const char* v = getenv("AZ_PERSIST")) s->persist = atoi(v);
     AZ_HIP(hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, device));
@@ -999,6 +1016,7 @@ int az_search_set_roots_from(az_search* s, const az_pos* start, const int32_t* h
     AZ_HIP(hipSetDevice(s->device));
     int rc = upload_histories(s, start, hist, off, game_id, noise_ply);
     if (rc) return rc;
+    if (adopt_net_generation(s)) return -1;
     rc = setup_roots(s, apply_noise, false);
     s->roots_fresh = rc == 0;
     return rc;
@@ -1022,6 +1040,7 @@ static int read_roots(az_search* s, float* improved, uint32_t* visits, int32_t* 
 
 int az_search_run(az_search* s, float* improved, uint32_t* visits, int32_t* depth) {
     if (!s) return fail("null search");
+    if (check_net_generation(s, "az_search_run")) return -1;
     if (!s->roots_fresh) return fail("az_search_run: set roots (az_search_set_roots / az_search_advance) first");
     s->roots_fresh = false;
     AZ_HIP(hipSetDevice(s->device));
@@ -1038,6 +1057,7 @@ int az_search_read_roots(az_search* s, float* improved, uint32_t* visits, int32_
 
 int az_search_advance(az_search* s, const int32_t* actions, int apply_noise, int32_t* result) {
     if (!s || !actions) return fail("null argument");
+    if (check_net_generation(s, "az_search_advance")) return -1;
     AZ_HIP(hipSetDevice(s->device));
     const int G = s->E.G;
     int *da = nullptr, *dr = nullptr;
@@ -1063,6 +1083,7 @@ int az_selfplay_reset(az_search* s) {
     AZ_HIP(hipSetDevice(s->device));
     int rc = upload_histories(s, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
+    if (adopt_net_generation(s)) return -1;
     AZ_HIP(hipMemset(s->E.ctr, 0, sizeof(Counters)));
     AZ_HIP(hipMemset(s->E.g_sims, 0, (size_t)s->E.G * 8));
     AZ_HIP(hipMemset(s->E.g_evals, 0, (size_t)s->E.G * 8));
@@ -1079,6 +1100,7 @@ int az_selfplay_reset(az_search* s) {
 static int selfplay_sims(az_search* s, int nsims, int* finished, int* active, int* move_done) {
     if (!s) return fail("null search");
     if (nsims <= 0) return fail("az_selfplay_run_sims: nsims must be > 0");
+    if (check_net_generation(s, "az_selfplay_step / az_selfplay_run_sims")) return -1;
     AZ_HIP(hipSetDevice(s->device));
     unsigned long long before = 0;
     AZ_HIP(hipMemcpy(&before, &s->E.ctr->games_finished, 8, hipMemcpyDeviceToHost));

@@ -3014,6 +3014,19 @@ int az_trainer_get_grads(az_trainer* t, float* out, size_t n) {
     return 0;
 }
 
+int az_net_update_from_trainer(az_net* net, az_trainer* t) {
+    if (!net || !t) return fail("az_net_update_from_trainer: null argument");
+    Trainer* T = t->t;
+    NetDev* d = net->dev;
+    if (T->device != d->device) return fail("az_net_update_from_trainer: the trainer and the net are on different devices");
+    if (T->blocks != d->blocks || T->F != d->filters)
+        return fail("az_net_update_from_trainer: the trainer is " + std::to_string(T->blocks) + "x" + std::to_string(T->F) +
+                    ", the net " + std::to_string(d->blocks) + "x" + std::to_string(d->filters));
+    AZ_HIP(hipSetDevice(T->device));
+    AZ_HIP(hipStreamSynchronize(T->st));      // everything queued on the trainer's stream first
+    return net_update_device(d, T->p, T->np, nullptr);
+}
+
 int az_trainer_relu_output(az_trainer* t, int layer, float* out, size_t n) {
     if (!t || !out) return fail("null");
     Trainer* T = t->t;

@@ -109,6 +109,32 @@ int az_net_forward(az_net* net, const float* planes, int n, float* policy, float
 /* Same on device pointers / a caller's hipStream_t (NULL = engine stream). */
 int az_net_forward_device(az_net* net, const float* d_planes, int n, float* d_policy, float* d_value,
                           void* stream);
+/* model.valid() without leaving the device (training.rs:83): rewrite every weight buffer of an existing
+ * net in place -- BatchNorm fold and all packed layouts, by HIP kernels (net_update.hip) -- from flat f32
+ * parameters (az_net_num_params layout) that are already in HBM on the net's device.  The buffers keep
+ * their addresses and sizes, and the result is byte for byte what az_net_create builds from the same
+ * parameters.  The work is ordered after what `stream` holds (NULL = the net's stream); the call returns
+ * when the new weights are in place.  n must be the net's parameter count, else an error and no change.
+ * No search may be running on the net; a search whose roots were set before the update must set roots
+ * (or az_selfplay_reset) again before it runs. */
+int az_net_update_device(az_net* net, const float* d_weights, size_t n, void* stream);
+/* the same from host weights: one upload, then the device path (a checkpoint, an arena opponent) */
+int az_net_update(az_net* net, const float* weights, size_t n);
+/* 0 after az_net_create, + 1 for each successful update */
+int64_t az_net_generation(az_net* net);
+/* the flat parameters of the last update (the net keeps a device copy from its first update on); an error
+ * for a net that was never updated (its creator holds those weights) */
+int az_net_get_weights(az_net* net, float* out, size_t n);
+/* Test hook: copy one packed weight buffer of the net to the host; returns its size in bytes (out NULL:
+ * the size alone), 0 for a buffer this net does not hold, < 0 on error (cap too small).  index = the conv
+ * (0 = input conv) for AZ_PACKED_CONV_W / CONV_B, the residual conv (0 .. 2 blocks - 1) for WINO_W /
+ * WINO16_W / WINO16_US (the conv's 1 / (Sa Sw), 4 bytes), 0 otherwise. */
+enum {
+    AZ_PACKED_CONV_W = 0, AZ_PACKED_CONV_B = 1, AZ_PACKED_IN_PK32 = 2, AZ_PACKED_WINO_W = 3, AZ_PACKED_WINO16_W = 4,
+    AZ_PACKED_WINO16_US = 5, AZ_PACKED_W8 = 6, AZ_PACKED_W8S = 7, AZ_PACKED_B8 = 8, AZ_PACKED_HEAD = 9,
+    AZ_PACKED_HEAD_FRAG = 10, AZ_PACKED_HEAD_FRAG32 = 11, AZ_PACKED_KINDS = 12
+};
+int az_net_packed_read(az_net* net, int kind, int index, void* out, size_t cap);
 
 /* ---- search: tree.rs MCTree + training.rs self-play driver ------------------------ */
 /* AZ_EVAL_NET: the engine's own az_net (fused HIP tower).  AZ_EVAL_SYNTHETIC: the hash evaluator
@@ -298,6 +324,10 @@ int az_trainer_step(az_trainer* t, const float* planes, const float* target_poli
 /* flat parameters (to build an az_net for self-play, or to save) / last gradients */
 int az_trainer_get_params(az_trainer* t, float* out, size_t n);
 int az_trainer_get_grads(az_trainer* t, float* out, size_t n);
+/* az_net_update_device from the trainer's device parameters (BatchNorm running statistics included),
+ * after everything queued on the trainer's stream: device to device, nothing goes to the host.  The
+ * trainer and the net must share the device and the blocks x filters shape. */
+int az_net_update_from_trainer(az_net* net, az_trainer* t);
 /* introspection for parity tests: the activation each ReLU of the last forward acted on, in
  * forward order -- layer 0 = input block output, 1..2B = residual blocks (h_b, x_b+1 NHWC
  * [B*64][F]), 2B+1 = head convs after BN+ReLU [B*64][64] (columns 0..39), 2B+2 =
