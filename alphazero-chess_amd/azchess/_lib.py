@@ -159,6 +159,19 @@ SIGNATURES = [
                                    P(AzPos)]),
     ("az_replay_save", C.c_int, [C.c_void_p, C.c_char_p]),
     ("az_replay_load", C.c_int, [C.c_char_p, C.c_int, P(C.c_void_p)]),
+    ("az_replay_create_on", C.c_int, [C.c_int, C.c_int, P(C.c_void_p)]),
+    ("az_replay_load_on", C.c_int, [C.c_char_p, C.c_int, C.c_int, P(C.c_void_p)]),
+    ("az_replay_device", C.c_int, [C.c_void_p]),
+    ("az_replay_sample_rows", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    ("az_trainer_compute_grads_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                  P(C.c_float)]),
+    ("az_trainer_step_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                         P(C.c_float)]),
+    ("az_trainer_compute_grads_replay", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int,
+                                                  P(C.c_float), P(C.c_int)]),
+    ("az_trainer_step_replay", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_double,
+                                         P(C.c_float), P(C.c_int)]),
     ("az_trainer_set_comm", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("az_trainer_set_host_reducer", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("az_trainer_set_sharded", C.c_int, [C.c_void_p, C.c_int]),

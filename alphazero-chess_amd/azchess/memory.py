@@ -23,14 +23,31 @@ class TrainingSample:              # memory.rs:11-16
     value: float
 
 
+def dev_ptr(x):
+    """A device address (or stream handle) for the C-ABI: an integer, a ctypes c_void_p, or an object
+    with data_ptr() (a torch tensor)."""
+    if x is None or isinstance(x, C.c_void_p):
+        return x
+    return C.c_void_p(int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))
+
+
 class ReplayBuffer:
-    def __init__(self, capacity=REPLAY_BUFFER_SIZE, _handle=None):
+    """device None: the host buffer.  device >= 0: the same buffer with its payload rows (policy,
+    value, position: 16,468 bytes per entry, allocated up front) in that GPU's HBM -- identical
+    results bit for bit, and Trainer.step_replay trains on it without a trip through the host."""
+
+    def __init__(self, capacity=REPLAY_BUFFER_SIZE, device=None, _handle=None):
         if _handle is None:
             h = C.c_void_p()
-            L.check(L.lib.az_replay_create(int(capacity), C.byref(h)))
+            if device is None:
+                L.check(L.lib.az_replay_create(int(capacity), C.byref(h)))
+            else:
+                L.check(L.lib.az_replay_create_on(int(capacity), int(device), C.byref(h)))
             _handle = h
         self._h = _handle
         self.capacity = capacity
+        dev = L.lib.az_replay_device(self._h)
+        self.device = None if dev < 0 else dev
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -72,6 +89,16 @@ class ReplayBuffer:
         assert got == n
         return planes, pol, val, [Position(L.AzPos.from_buffer_copy(states[i])) for i in range(n)]
 
+    def sample_rows(self, batch_size, seed, planes=None, policy=None, value=None, lo=0, hi=None, stream=None):
+        """Rows [lo, hi) of sample_arrays' draw to device memory of a device-backed buffer (addresses
+        or objects with data_ptr(); None skips an output): planes [hi-lo,19,64], policy [hi-lo,4096],
+        value [hi-lo] f32, row lo first, ordered on `stream` (None: the buffer's own, complete on
+        return).  Returns the number of rows drawn, min(batch_size, len)."""
+        n = min(batch_size, len(self))
+        return L.check(L.lib.az_replay_sample_rows(self._h, int(batch_size), C.c_uint64(seed & (2 ** 64 - 1)), int(lo),
+                                                   n if hi is None else int(hi), dev_ptr(planes), dev_ptr(policy),
+                                                   dev_ptr(value), dev_ptr(stream)))
+
     def sample(self, batch_size, seed=0):
         _, pol, val, states = self.sample_arrays(batch_size, seed)
         return [TrainingSample(s, p, float(v)) for s, p, v in zip(states, pol, val)]
@@ -80,9 +107,12 @@ class ReplayBuffer:
         L.check(L.lib.az_replay_save(self._h, str(path).encode()))
 
     @staticmethod
-    def load(path, capacity=REPLAY_BUFFER_SIZE):
+    def load(path, capacity=REPLAY_BUFFER_SIZE, device=None):
         h = C.c_void_p()
-        L.check(L.lib.az_replay_load(str(path).encode(), int(capacity), C.byref(h)))
+        if device is None:
+            L.check(L.lib.az_replay_load(str(path).encode(), int(capacity), C.byref(h)))
+        else:
+            L.check(L.lib.az_replay_load_on(str(path).encode(), int(capacity), int(device), C.byref(h)))
         return ReplayBuffer(capacity, _handle=h)
 
 

@@ -181,6 +181,42 @@ class Trainer:
                                           float(lr), L.fptr(loss)))
         return float(loss[0]), float(loss[1])
 
+    def compute_grads_device(self, planes, tpol, tval, batch):
+        """compute_gradients on inputs already in this GPU's memory (addresses or objects with
+        data_ptr(), complete when the call is made): planes [batch,19,64], policy [batch,4096],
+        value [batch] f32."""
+        from .memory import dev_ptr
+        loss = np.zeros(2, np.float32)
+        self._check(L.lib.az_trainer_compute_grads_device(self._h, dev_ptr(planes), dev_ptr(tpol), dev_ptr(tval),
+                                                          int(batch), L.fptr(loss)))
+        return float(loss[0]), float(loss[1])
+
+    def step_device(self, planes, tpol, tval, batch, lr):
+        """step on inputs already in this GPU's memory (as compute_grads_device): bit for bit
+        step() on the same data."""
+        from .memory import dev_ptr
+        loss = np.zeros(2, np.float32)
+        self._check(L.lib.az_trainer_step_device(self._h, dev_ptr(planes), dev_ptr(tpol), dev_ptr(tval), int(batch),
+                                                 float(lr), L.fptr(loss)))
+        return float(loss[0]), float(loss[1])
+
+    def compute_grads_replay(self, replay, batch_size, seed, lo=0, hi=None):
+        """compute_gradients on rows [lo, hi) (hi None: all) of replay.sample_arrays(batch_size,
+        seed)'s draw, gathered on the device from a device-backed ReplayBuffer of this GPU."""
+        loss = np.zeros(2, np.float32)
+        self._check(L.lib.az_trainer_compute_grads_replay(self._h, replay._h, int(batch_size),
+                                                          C.c_uint64(seed & (2 ** 64 - 1)), int(lo),
+                                                          -1 if hi is None else int(hi), L.fptr(loss), None))
+        return float(loss[0]), float(loss[1])
+
+    def step_replay(self, replay, batch_size, seed, lr, lo=0, hi=None):
+        """step on rows [lo, hi) of the same draw: bit for bit
+        step(*[a[lo:hi] for a in replay.sample_arrays(batch_size, seed)[:3]], lr)."""
+        loss = np.zeros(2, np.float32)
+        self._check(L.lib.az_trainer_step_replay(self._h, replay._h, int(batch_size), C.c_uint64(seed & (2 ** 64 - 1)),
+                                                 int(lo), -1 if hi is None else int(hi), float(lr), L.fptr(loss), None))
+        return float(loss[0]), float(loss[1])
+
     def params(self):
         out = np.empty(self.n, np.float32)
         L.check(L.lib.az_trainer_get_params(self._h, L.fptr(out), self.n))
@@ -305,7 +341,7 @@ def _default_allgather():
 def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPISODES, sims=NUM_SIMULATIONS,
           min_replay=MIN_REPLAY_SIZE, train_steps=NUM_TRAIN_STEPS, batch_size=BATCH_SIZE, replay=None, trainer=None,
           device=0, seed=SEED, dtype="f32", comm=None, shard_batch=None, reducer=None, shared_replay=None,
-          allgather=None, log=None, log_batch=None):
+          allgather=None, log=None, log_batch=None, device_replay=False):
     """train() (training.rs:39-275) without the TUI, arena and Elo (SKIP_VALIDATION = true,
     parameters.rs:35): per iteration, self-play `games` games with model.valid() until the replay
     buffer holds min_replay unique positions, then train_steps AdamW steps on batches of
@@ -326,7 +362,11 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
     Labelled opt-ins: shard_batch=False trains batch_size per rank (global batch batch_size x world,
     per-rank BatchNorm, averaged gradients); shared_replay=False keeps one buffer per rank.
     log_batch(iteration, step, planes, policy, value, lo, hi): each step's drawn batch and this
-    rank's rows of it.  Returns (trainer, replay, per-iteration stats)."""
+    rank's rows of it.
+    device_replay (opt-in): the replay buffer's payload lives in `device`'s HBM (ReplayBuffer(device=))
+    and each step gathers its rows there (Trainer.step_replay) instead of sampling to the host and
+    uploading; the buffer equals the host one bit for bit, so every result is the same.  A caller's
+    `replay` is used as it is.  Returns (trainer, replay, per-iteration stats)."""
     from .memory import ReplayBuffer, add_from_ranks
     if comm and reducer:
         raise ValueError("train: comm (RCCL) or reducer (host), not both")
@@ -346,7 +386,10 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
         elif reducer:
             trainer.set_host_reducer(*reducer)
     trainer.set_sharded(shard_batch)   # a caller's trainer too (its comm / reducer is the caller's)
-    replay = replay if replay is not None else ReplayBuffer()
+    if replay is None:
+        replay = ReplayBuffer(device=device) if device_replay else ReplayBuffer()
+    elif device_replay and replay.device is None:
+        raise ValueError("train: device_replay with a host-backed replay buffer")
     history = []
     model = None
     for iteration in range(iterations):
@@ -391,6 +434,23 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
         lr = get_cyclical_lr(iteration)
         pl_sum = vl_sum = 0.0
         for b in range(train_steps):
+            if device_replay:   # the same draws and rows as below, gathered in HBM into the trainer's inputs
+                if shared_replay and shard_batch:
+                    n, s = batch_size, sample_seed(seed, iteration, b)
+                    lo, hi = shard_bounds(min(n, len(replay)), rank, world)
+                    if hi <= lo:
+                        raise ValueError("train: a %d-position batch leaves rank %d no rows" % (min(n, len(replay)), rank))
+                else:
+                    n = -(-batch_size // world) if shard_batch else batch_size
+                    s = sample_seed(seed, iteration, b, rank)
+                    lo, hi = 0, min(n, len(replay))
+                if log_batch:
+                    planes, pol, val, _ = replay.sample_arrays(n, seed=s)
+                    log_batch(iteration, b, planes, pol, val, lo, hi)
+                pl, vl = trainer.step_replay(replay, n, s, lr, lo, hi)
+                pl_sum += pl
+                vl_sum += vl
+                continue
             if shared_replay and shard_batch:     # one global batch, this rank's slice
                 planes, pol, val, _ = replay.sample_arrays(batch_size, seed=sample_seed(seed, iteration, b))
                 lo, hi = shard_bounds(planes.shape[0], rank, world)

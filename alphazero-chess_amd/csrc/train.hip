@@ -2539,8 +2539,10 @@ int bias_grad(Trainer* T, const float* dy, int ld, int C, int R, float* dst) {
 
 // defer_loss (az_trainer_step, sharded): the losses' exchange rides in the gradient all-reduce of
 // the trainer_apply that follows (one dependent collective fewer); they are written there
+// on_device: the three inputs are already in HBM on the trainer's device (copied device to device, or
+// used in place where they are the trainer's own input buffers)
 int trainer_grads(Trainer* T, const float* planes, const float* tpol, const float* tval, int B, float* losses,
-                  bool defer_loss = false) {
+                  bool defer_loss = false, bool on_device = false) {
     if (B < 1 || B > T->Bmax) return fail("train: batch size out of range");
     T->last_batch = B;
     // the current device is per host thread (ranks as threads start on device 0): set it before
@@ -2551,9 +2553,10 @@ int trainer_grads(Trainer* T, const float* planes, const float* tpol, const floa
     const int F = T->F, R = B * 64;
     hipStream_t st = T->st;
     const Layout& L = T->L;
-    AZ_HIP(hipMemcpyAsync(T->planes, planes, (size_t)B * 19 * 64 * sizeof(float), hipMemcpyHostToDevice, st));
-    AZ_HIP(hipMemcpyAsync(T->tpol, tpol, (size_t)B * 4096 * sizeof(float), hipMemcpyHostToDevice, st));
-    AZ_HIP(hipMemcpyAsync(T->tval, tval, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
+    const hipMemcpyKind up = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (planes != T->planes) AZ_HIP(hipMemcpyAsync(T->planes, planes, (size_t)B * 19 * 64 * sizeof(float), up, st));
+    if (tpol != T->tpol) AZ_HIP(hipMemcpyAsync(T->tpol, tpol, (size_t)B * 4096 * sizeof(float), up, st));
+    if (tval != T->tval) AZ_HIP(hipMemcpyAsync(T->tval, tval, (size_t)B * sizeof(float), up, st));
     AZ_HIP(hipMemsetAsync(T->g, 0, T->np * sizeof(float), st));
     // weights of this step in GEMM layouts
     if (T->wino && T->blocks > 0) {  // residual convs: Winograd weights, forward and data grad, one launch
@@ -2996,6 +2999,71 @@ int az_trainer_step(az_trainer* t, const float* planes, const float* target_poli
         losses[1] = t->t->loss_out[1];
     }
     return 0;
+}
+
+static int trainer_step_from(Trainer* T, const float* planes, const float* tpol, const float* tval, int batch, double lr,
+                             float* losses) {
+    if (trainer_grads(T, planes, tpol, tval, batch, losses, true, true) != 0) return -1;
+    const bool lx = T->loss_in_grad;
+    if (trainer_apply(T, lr) != 0) return -1;
+    if (lx && losses) {
+        losses[0] = T->loss_out[0];
+        losses[1] = T->loss_out[1];
+    }
+    return 0;
+}
+
+int az_trainer_compute_grads_device(az_trainer* t, const float* d_planes, const float* d_policy, const float* d_value,
+                                    int batch, float* losses) {
+    if (!t || !d_planes || !d_policy || !d_value) return fail("null");
+    return trainer_grads(t->t, d_planes, d_policy, d_value, batch, losses, false, true);
+}
+
+int az_trainer_step_device(az_trainer* t, const float* d_planes, const float* d_policy, const float* d_value, int batch,
+                           double lr, float* losses) {
+    if (!t || !d_planes || !d_policy || !d_value) return fail("null");
+    return trainer_step_from(t->t, d_planes, d_policy, d_value, batch, lr, losses);
+}
+
+// rows [lo, hi) of the buffer's draw into the trainer's own inputs, on the trainer's stream; every check
+// comes before the first launch.  Returns the row count, < 0 on error.
+static int trainer_gather_replay(az_trainer* t, az_replay* r, int batch, uint64_t seed, int lo, int hi, int* drawn) {
+    if (!r || batch < 0) return fail("az_trainer_*_replay: bad arguments");
+    const int dev = az_replay_device(r);
+    if (dev == AZ_DEVICE_HOST) return fail("az_trainer_*_replay: the replay buffer is host-backed (az_replay_create_on a device)");
+    if (!t) return fail("az_trainer_*_replay: null trainer");
+    Trainer* T = t->t;
+    if (dev != T->device)
+        return fail("az_trainer_*_replay: the buffer is on device " + std::to_string(dev) + ", the trainer on " +
+                    std::to_string(T->device));
+    const int len = az_replay_len(r);
+    if (len < 1) return fail("az_trainer_*_replay: the replay buffer is empty");
+    const int n = std::min(batch, len);
+    if (hi < 0) hi = n;
+    if (lo < 0 || lo > hi || hi > n)
+        return fail("az_trainer_*_replay: rows [" + std::to_string(lo) + ", " + std::to_string(hi) + ") of a draw of " +
+                    std::to_string(n));
+    if (hi - lo < 1 || hi - lo > T->Bmax) return fail("train: batch size out of range");
+    AZ_HIP(hipSetDevice(T->device));
+    if (az_replay_sample_rows(r, batch, seed, lo, hi, T->planes, T->tpol, T->tval, T->st) != n) return -1;
+    if (drawn) *drawn = n;
+    return hi - lo;
+}
+
+int az_trainer_compute_grads_replay(az_trainer* t, az_replay* r, int batch, uint64_t seed, int lo, int hi, float* losses,
+                                    int* drawn) {
+    const int B = trainer_gather_replay(t, r, batch, seed, lo, hi, drawn);
+    if (B < 0) return -1;
+    Trainer* T = t->t;
+    return trainer_grads(T, T->planes, T->tpol, T->tval, B, losses, false, true);
+}
+
+int az_trainer_step_replay(az_trainer* t, az_replay* r, int batch, uint64_t seed, int lo, int hi, double lr,
+                           float* losses, int* drawn) {
+    const int B = trainer_gather_replay(t, r, batch, seed, lo, hi, drawn);
+    if (B < 0) return -1;
+    Trainer* T = t->t;
+    return trainer_step_from(T, T->planes, T->tpol, T->tval, B, lr, losses);
 }
 
 int az_trainer_get_params(az_trainer* t, float* out, size_t n) {

@@ -388,6 +388,42 @@ int az_replay_sample(az_replay* r, int batch, uint64_t seed, float* planes, floa
 /* save / load (memory.rs:107-117): bincode 2 standard-config file of the reference's layout */
 int az_replay_save(const az_replay* r, const char* path);
 int az_replay_load(const char* path, int capacity, az_replay** out);
+/* The same buffer with its payload in HBM (device >= 0; AZ_DEVICE_HOST, below: az_replay_create /
+ * az_replay_load as they are).  The host keeps the keys (FEN strings), the FIFO order, the visit counts and
+ * the key -> slot map; each of `capacity` slots on the device holds an entry's policy [4096] f32, its value
+ * and the az_pos rebuilt from its key (what az_replay_sample returns): capacity x 16,468 bytes, allocated
+ * here -- if that fails, or `device` is not one az_device_count lists, an error and no handle.  Every
+ * az_replay_* call above works on such a handle with results identical to the host buffer's, bit for bit
+ * (entries, running means, FIFO order, samples, save file, return values; az_replay_add_many applies the
+ * steps before a bad one and then fails): adds upload the compact records (AZ_REPLAY_ADD_CHUNK steps per
+ * launch: environment, read per call, default 256, at least 1; no result depends on it) and are complete
+ * when the call returns; az_replay_sample gathers on the device and reads back once. */
+int az_replay_create_on(int capacity, int device, az_replay** out);
+int az_replay_load_on(const char* path, int capacity, int device, az_replay** out);
+int az_replay_device(const az_replay* r);                           /* the device, or AZ_DEVICE_HOST */
+/* az_replay_sample's draw (the same partial Fisher-Yates, n = min(batch, len)); rows [lo, hi) of it go to
+ * device pointers on the buffer's device (any may be NULL), row lo at index 0: planes [hi-lo,19,64], policy
+ * [hi-lo,4096] (16-byte aligned), value [hi-lo].  The work is ordered on `stream` (a hipStream_t; NULL = the
+ * buffer's own stream, then complete on return).  Returns n.  0 <= lo <= hi <= n, else an error and nothing
+ * is written; a host-backed handle is an error. */
+int az_replay_sample_rows(az_replay* r, int batch, uint64_t seed, int lo, int hi, float* d_planes, float* d_policy,
+                          float* d_value, void* stream);
+/* az_trainer_compute_grads / az_trainer_step with the inputs already in HBM on the trainer's device: the
+ * uploads become device-to-device copies on the trainer's stream (skipped for the trainer's own input
+ * buffers), everything after them is the same, so a step is bit-identical to az_trainer_step on the same
+ * data.  The inputs must be complete when the call is made. */
+int az_trainer_compute_grads_device(az_trainer* t, const float* d_planes, const float* d_policy, const float* d_value,
+                                    int batch, float* losses);
+int az_trainer_step_device(az_trainer* t, const float* d_planes, const float* d_policy, const float* d_value, int batch,
+                           double lr, float* losses);
+/* The same fed by a device-backed buffer: rows [lo, hi) (hi < 0: n) of az_replay_sample_rows' draw are
+ * gathered straight into the trainer's inputs on the trainer's stream, then the step runs; *drawn (may be
+ * NULL) = n.  Errors, with nothing changed: the buffer is host-backed, on another device than the trainer,
+ * or empty; rows outside 0 <= lo < hi <= n; more than the trainer's max_batch rows. */
+int az_trainer_compute_grads_replay(az_trainer* t, az_replay* r, int batch, uint64_t seed, int lo, int hi, float* losses,
+                                    int* drawn);
+int az_trainer_step_replay(az_trainer* t, az_replay* r, int batch, uint64_t seed, int lo, int hi, double lr,
+                           float* losses, int* drawn);
 
 /* ---- test hook: the device rules path (parity tests; the engine never calls it) ----------
  * Runs, on the GPU, exactly what a leaf expansion runs (index_to_move + play, chess.rs:118-171 /
