@@ -69,6 +69,17 @@ class AzTiming(C.Structure):
                 ("rows", C.c_int64)]
 
 
+class AzArenaPlayer(C.Structure):
+    _fields_ = [("kind", C.c_int), ("net", C.c_void_p), ("depth", C.c_int)]
+
+
+class AzArenaCfg(C.Structure):
+    _fields_ = [("games", C.c_int), ("sims", C.c_int), ("num_stochastic_moves", C.c_int), ("c_puct", C.c_float),
+                ("seed", C.c_uint64)]
+
+
+PLAYER_MCTS, PLAYER_BASE, PLAYER_MINIMAX, PLAYER_RANDOM, PLAYER_EXTERNAL = 0, 1, 2, 3, 4
+
 # az_eval_fn (include/az.h): int (*)(void* ctx, const az_pos*, int n, float* policy, float* value)
 EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(AzPos), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float))
 
@@ -186,6 +197,15 @@ SIGNATURES = [
     ("az_minimax_scores", C.c_int, [C.c_int, P(AzPos), C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), P(C.c_int32),
                                     P(C.c_int32), P(C.c_int64)]),
     ("az_minimax_best", C.c_int, [P(C.c_int32), C.c_int, C.c_float]),
+    ("az_arena_create", C.c_int, [P(AzArenaPlayer), P(AzArenaPlayer), P(AzArenaCfg), C.c_int, P(C.c_void_p)]),
+    ("az_arena_destroy", C.c_int, [C.c_void_p]),
+    ("az_arena_reset", C.c_int, [C.c_void_p, P(AzPos), C.c_uint64]),
+    ("az_arena_step", C.c_int, [C.c_void_p, P(C.c_float), P(C.c_int32), P(C.c_int)]),
+    ("az_arena_results", C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32)]),
+    ("az_arena_live", C.c_int, [C.c_void_p, P(C.c_int32)]),
+    ("az_arena_history", C.c_int, [C.c_void_p, C.c_int, P(C.c_int32), C.c_int]),
+    ("az_arena_stats", C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
+    ("az_arena_choose", C.c_int, [P(C.c_float), C.c_int, C.c_int, C.c_float]),
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -14,8 +14,8 @@ import numpy as np
 
 from . import _lib as L
 from .chess import Position, to_tensor
-from .parameters import (BATCH_SIZE, MIN_REPLAY_SIZE, NUM_EPISODES, NUM_FILTERS, NUM_RES_BLOCKS, NUM_SIMULATIONS,
-                         NUM_TRAIN_STEPS, SEED)
+from .parameters import (BATCH_SIZE, EVALUATION_GAMES, MIN_REPLAY_SIZE, NUM_EPISODES, NUM_FILTERS, NUM_RES_BLOCKS,
+                         NUM_SIMULATIONS, NUM_TRAIN_STEPS, SEED)
 from .tree import BatchedSearch
 
 
@@ -324,6 +324,11 @@ def sample_seed(seed, iteration, step, rank=None):
     return s if rank is None else s ^ rank << 40
 
 
+def elo_seed(seed, iteration):
+    """Seed of an iteration's Elo match (train(elo_evaluator=...))."""
+    return (seed << 20) ^ (iteration << 8) ^ 0xE10
+
+
 def shard_bounds(n, rank, world):
     """This rank's contiguous rows [lo, hi) of an n-row global batch."""
     return rank * n // world, (rank + 1) * n // world
@@ -341,11 +346,13 @@ def _default_allgather():
 def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPISODES, sims=NUM_SIMULATIONS,
           min_replay=MIN_REPLAY_SIZE, train_steps=NUM_TRAIN_STEPS, batch_size=BATCH_SIZE, replay=None, trainer=None,
           device=0, seed=SEED, dtype="f32", comm=None, shard_batch=None, reducer=None, shared_replay=None,
-          allgather=None, log=None, log_batch=None, device_replay=False):
-    """train() (training.rs:39-275) without the TUI, arena and Elo (SKIP_VALIDATION = true,
-    parameters.rs:35): per iteration, self-play `games` games with model.valid() until the replay
-    buffer holds min_replay unique positions, then train_steps AdamW steps on batches of
-    batch_size at get_cyclical_lr(iteration); the new model replaces the old one.
+          allgather=None, log=None, log_batch=None, device_replay=False, elo_evaluator=None,
+          elo_games=EVALUATION_GAMES, elo_base=150.0):
+    """train() (training.rs:39-275) without the TUI.  Per iteration: self-play `games` games with
+    model.valid() until the replay buffer holds min_replay unique positions, then train_steps AdamW
+    steps on batches of batch_size at get_cyclical_lr(iteration); the new model replaces the old one.
+    The arena is off by default (SKIP_VALIDATION = true, parameters.rs:35); elo_evaluator, below,
+    turns on the Elo step.
 
     Data parallel (comm = (unique_id, rank, world) over RCCL, or reducer = (reduce, rank, world)
     through a host callback, Trainer.set_host_reducer): every rank plays its own games (seed offset
@@ -366,7 +373,15 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
     device_replay (opt-in): the replay buffer's payload lives in `device`'s HBM (ReplayBuffer(device=))
     and each step gathers its rows there (Trainer.step_replay) instead of sampling to the host and
     uploading; the buffer equals the host one bit for bit, so every result is the same.  A caller's
-    `replay` is used as it is.  Returns (trainer, replay, per-iteration stats)."""
+    `replay` is used as it is.
+    elo_evaluator (opt-in; None: no arena, as before): an AlphaZero net to rate the model against.  Each
+    iteration then ends with the reference's tail (training.rs:234-251): the model is refreshed in place
+    from the trainer and compute_elo_rankings([Player.base(elo_evaluator), Player.base(model)], elo_base,
+    games=elo_games, engine=True, seed=elo_seed(seed, iteration)) plays its match in the engine arena
+    (validation.Arena); the iteration's entry gains `elos`, `winrate_matrix`, `arena_avg_batch` and
+    `arena_s`.  Nothing else changes: the evaluator is not replaced and no model is rejected -- the
+    WIN_RATE_THRESHOLD gate (training.rs:208-232) needs a trainer that can take parameters back, an
+    entry point the library does not have.  Returns (trainer, replay, per-iteration stats)."""
     from .memory import ReplayBuffer, add_from_ranks
     if comm and reducer:
         raise ValueError("train: comm (RCCL) or reducer (host), not both")
@@ -472,6 +487,14 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
               "games_finished": finished, "episode_steps": steps_done, "moves": moves_done,
               "shared_replay": shared_replay and world > 1, "shard_batch": shard_batch,
               "episode_steps_global": steps_global if shared_replay and world > 1 else steps_done}
+        if elo_evaluator is not None:
+            from .validation import Player, compute_elo_rankings
+            model = trainer.model(dtype, into=model)
+            avg, elos, wm = compute_elo_rankings([Player.base(elo_evaluator), Player.base(model)], elo_base,
+                                                 games=elo_games, engine=True, seed=elo_seed(seed, iteration),
+                                                 device=device)
+            st.update(elos=[float(e) for e in elos], winrate_matrix=wm, arena_avg_batch=avg,
+                      arena_s=time.perf_counter() - t2)
         history.append(st)
         if log:
             log(st)

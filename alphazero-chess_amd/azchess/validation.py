@@ -15,14 +15,19 @@ A MiniMax(n) player (chess.rs:248-322, validation.rs:113) scores all of its game
 az_minimax_scores call -- the batched negamax kernels on the GPU, or the same search on the host
 with device=-1 -- and takes one of the best entries with the same seeded stream; it runs no network,
 so it adds nothing to num_inferences.  The human player (chess.rs:325-420, validation.rs:91-111) is
-out of scope.
+out of scope; Player.external() is its seat in the engine arena (the caller supplies the move).
+`Arena` is the same match with its games in HBM (libaz az_arena_*: one az_arena_step per ply, move
+generation, choice, play_move and the histories on the device); evaluate(..., engine=True) plays through
+it with the same seeded uniforms and returns the same moves, results and statistics.
 """
+import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from .chess import GameState, minimax_best, minimax_scores, play_move, to_tensor
-from .parameters import EVALUATION_GAMES, NUM_SIMULATIONS, TEMPERATURE_ANNEALING
+from . import _lib as L
+from .chess import GameState, minimax_best, minimax_scores, play_move, positions_to_array, to_tensor
+from .parameters import C_PUCT, EVALUATION_GAMES, NUM_SIMULATIONS, TEMPERATURE_ANNEALING
 from .tree import BatchedSearch
 
 
@@ -38,7 +43,7 @@ class EvaluationResult:             # validation.rs:12-19
 
 class Player:                       # validation.rs:21-27 (MctsModel, BaseModel, MiniMax, Random)
     def __init__(self, kind, model=None, depth=None, device=None):
-        assert kind in ("mcts", "base", "random", "minimax")
+        assert kind in ("mcts", "base", "random", "minimax", "external")
         self.kind, self.model, self.depth, self.device = kind, model, depth, device
 
     @staticmethod
@@ -58,6 +63,12 @@ class Player:                       # validation.rs:21-27 (MctsModel, BaseModel,
     def minimax(depth=4, device=None):
         """Player::MiniMax(depth); device=None searches on evaluate's device, -1 on the host."""
         return Player("minimax", depth=depth, device=device)
+
+    @staticmethod
+    def external():
+        """A seat whose moves the caller passes to Arena.step (the reference's Player::Human, or any
+        caller-side bot); only the engine arena has it."""
+        return Player("external")
 
 
 def argmax_last(v):
@@ -89,11 +100,125 @@ def choose(policy, fullmoves, num_stochastic_moves, u):
     return weighted_index(policy, u)
 
 
+_KINDS = {"mcts": L.PLAYER_MCTS, "base": L.PLAYER_BASE, "minimax": L.PLAYER_MINIMAX, "random": L.PLAYER_RANDOM,
+          "external": L.PLAYER_EXTERNAL}
+
+
+class Arena:
+    """az_arena: `games` evaluation games in HBM, player_1 White in the even games; step() plays one ply
+    of every live game on the device.  A MiniMax player searches on the arena's device."""
+
+    def __init__(self, player_1, player_2, games=EVALUATION_GAMES, sims=NUM_SIMULATIONS,
+                 num_stochastic_moves=TEMPERATURE_ANNEALING, seed=0, device=0, c_puct=C_PUCT):
+        self.games = games
+        self._players = (player_1, player_2)          # keeps the nets alive as long as the handle
+
+        def rec(p):
+            net = p.model._h if p.kind in ("mcts", "base") and p.model is not None else None
+            return L.AzArenaPlayer(_KINDS[p.kind], net, int(p.depth or 0))
+        r1 = rec(player_1)
+        r2 = r1 if player_1 is player_2 else rec(player_2)
+        cfg = L.AzArenaCfg(games, sims, num_stochastic_moves, c_puct, seed)
+        h = C.c_void_p()
+        L.check(L.lib.az_arena_create(C.byref(r1), C.byref(r2), C.byref(cfg), device, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            L.lib.az_arena_destroy(self._h)
+        except Exception:
+            pass
+
+    def reset(self, start=None, seed=0):
+        """Every game back to live with empty histories; start: `games` Positions (or an az_pos array),
+        None = the start position."""
+        st = None
+        if start is not None:
+            arr = start if isinstance(start, np.ndarray) else positions_to_array(start)
+            arr = np.ascontiguousarray(arr, L.POS_DTYPE)
+            assert len(arr) == self.games
+            st = arr.ctypes.data_as(C.POINTER(L.AzPos))
+        L.check(L.lib.az_arena_reset(self._h, st, int(seed)))
+
+    def step(self, u=None, actions=None):
+        """One ply of every live game; u [games] float32 uniforms (None: the engine's stream), actions
+        [games] for external movers.  Returns the number of games still going."""
+        up = ap = None
+        if u is not None:
+            u = np.ascontiguousarray(u, np.float32)
+            assert u.size == self.games
+            up = L.fptr(u)
+        if actions is not None:
+            actions = np.ascontiguousarray(actions, np.int32)
+            assert actions.size == self.games
+            ap = L.i32ptr(actions)
+        live = C.c_int()
+        L.check(L.lib.az_arena_step(self._h, up, ap, C.byref(live)))
+        return live.value
+
+    def results(self):
+        """(result [games]: ONGOING / DRAW / WHITE_WINS / BLACK_WINS, plies [games])"""
+        res = np.zeros(self.games, np.int32)
+        plies = np.zeros(self.games, np.int32)
+        L.check(L.lib.az_arena_results(self._h, L.i32ptr(res), L.i32ptr(plies)))
+        return res, plies
+
+    def live(self):
+        """bool [games]: the games still going, as the last step read them back (no device access)."""
+        out = np.zeros(self.games, np.int32)
+        L.check(L.lib.az_arena_live(self._h, L.i32ptr(out)))
+        return out != 0
+
+    def history(self, game):
+        out = np.zeros(512, np.int32)
+        n = L.check(L.lib.az_arena_history(self._h, int(game), L.i32ptr(out), out.size))
+        return [int(a) for a in out[:n]]
+
+    def stats(self):
+        """(num_inferences, rows) since the last reset (validation.rs:209-254)."""
+        a, b = C.c_double(), C.c_double()
+        L.check(L.lib.az_arena_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
+def arena_choose(policy, fullmoves, num_stochastic_moves, u):
+    """az_arena_choose: `choose` in libaz (the rule the arena kernels apply)."""
+    p = np.ascontiguousarray(policy, np.float32)
+    assert p.size == L.ACTION_SPACE
+    return int(L.check(L.lib.az_arena_choose(L.fptr(p), int(fullmoves), int(num_stochastic_moves), C.c_float(u))))
+
+
+def _evaluate_engine(player_1, player_2, G, sims, num_stochastic_moves, seed, device, max_plies, record):
+    arena = Arena(player_1, player_2, games=G, sims=sims, num_stochastic_moves=num_stochastic_moves, seed=seed,
+                  device=device)
+    u = np.zeros(G, np.float32)
+    live = np.ones(G, bool)
+    for ply in range(max_plies):
+        for g in np.flatnonzero(live):
+            u[g] = choice_uniform(seed, int(g), ply)
+        if arena.step(u) == 0:
+            break
+        live = arena.live()
+    res, _ = arena.results()
+    result = [{L.DRAW: 0, L.WHITE_WINS: 1, L.BLACK_WINS: -1}.get(int(r)) for r in res]
+    num_inferences, rows = arena.stats()
+    hist = [arena.history(g) for g in range(G)] if record else None
+    return result, hist, num_inferences, rows
+
+
 def evaluate(player_1, player_2, games=EVALUATION_GAMES, sims=NUM_SIMULATIONS,
-             num_stochastic_moves=TEMPERATURE_ANNEALING, seed=0, device=0, max_plies=1000, record=False):
+             num_stochastic_moves=TEMPERATURE_ANNEALING, seed=0, device=0, max_plies=1000, record=False,
+             engine=False):
     """validation.rs:155-282.  Returns EvaluationResult (and the games' move lists and results
-    when record=True)."""
+    when record=True).  engine=True: the match runs through Arena (games in HBM, one az_arena_step per
+    ply) with the same per-(game, ply) uniforms -- the same moves, results and statistics for MCTS,
+    base-model and MiniMax players (a MiniMax player then searches on `device`; a random player draws
+    with the game's uniform instead of this loop's per-ply generator)."""
     G = games
+    if engine:
+        result, hist, num_inferences, rows = _evaluate_engine(player_1, player_2, G, sims, num_stochastic_moves,
+                                                              seed, device, max_plies, record)
+        return _evaluation_result(result, G, num_inferences, rows, hist, record)
     states = [GameState() for _ in range(G)]
     hist = [[] for _ in range(G)]
     result = [None] * G                           # White's result: 1, 0, -1
@@ -163,6 +288,10 @@ def evaluate(player_1, player_2, games=EVALUATION_GAMES, sims=NUM_SIMULATIONS,
                 result[g] = -1
             elif r != 0:
                 raise RuntimeError("player played an illegal move")
+    return _evaluation_result(result, G, num_inferences, rows, hist, record)
+
+
+def _evaluation_result(result, G, num_inferences, rows, hist, record):
     p1_score = [(r if g % 2 == 0 else -r) for g, r in enumerate(result) if r is not None]
     p1_wins = sum(1 for r in p1_score if r > 0)
     draws = sum(1 for r in p1_score if r == 0)
@@ -194,7 +323,8 @@ def compute_elos(winrate_matrix, base_elo):
 
 
 def compute_elo_rankings(players, base_elo=150.0, **kw):
-    """ratings.rs:5-28: round robin, winrate matrix, Elo.  Returns (avg_batch_size, elos, matrix)."""
+    """ratings.rs:5-28: round robin, winrate matrix, Elo.  Returns (avg_batch_size, elos, matrix).
+    Keywords go to evaluate (engine=True: every match through the engine arena)."""
     n = len(players)
     wm = [[0.5] * n for _ in range(n)]
     ninf, avg = 0.0, 0.0

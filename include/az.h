@@ -494,6 +494,59 @@ int az_minimax_scores(int device, const az_pos* pos, int n, int depth, int32_t* 
  * -1 if nmoves == 0. */
 int az_minimax_best(const int32_t* scores, int nmoves, float u);
 
+/* ---- evaluation arena on the device: validation.rs:155-402 evaluate / play_evaluation_game --------
+ * `games` games in lockstep whose positions, position histories (the repetition multisets), move lists
+ * and results live in HBM; az_arena_step plays one ply of every live game.  Game g has player 1 as White
+ * when g is even and as Black when g is odd.  A move's result is play_move's (chess.rs:36-63): outcome()
+ * first, then the position enters the multiset, then a draw at count >= 3, halfmoves >= 100 or
+ * fullmoves >= 200. */
+enum { AZ_PLAYER_MCTS = 0, AZ_PLAYER_BASE = 1, AZ_PLAYER_MINIMAX = 2, AZ_PLAYER_RANDOM = 3, AZ_PLAYER_EXTERNAL = 4 };
+/* net: the MCTS and base-model players' network (NULL for an MCTS player: the synthetic evaluator);
+ * depth: a MiniMax player's depth */
+typedef struct { int kind; az_net* net; int depth; } az_arena_player;
+typedef struct { int games, sims, num_stochastic_moves; float c_puct; uint64_t seed; } az_arena_cfg;
+typedef struct az_arena az_arena;
+/* p1 == p2 (the same pointer): one player on both sides.  Per mover kind:
+ *   BASE      the net's policy row of the current position at the legal move indices, then az_arena_choose's
+ *             rule with u[g]; num_inferences += 1 per ply and net, rows += games to move
+ *   MCTS      a fresh noiseless tree from the current state with its repetition history
+ *             (MCTree::async_init(.., false)), `sims` simulations, the same rule over the improved policy
+ *             (the f32 values az_search_read_roots returns); num_inferences += sims + 1.  The arena owns one
+ *             az_search per MCTS player ((games + 1) / 2 slots, `games` when it plays both colours, no FEN
+ *             cache); spare slots repeat the first game's root, and rows counts their evaluations too
+ *   MINIMAX   az_minimax_scores at `depth` on the arena's device, then az_minimax_best(scores, nmoves, u[g])
+ *   RANDOM    entry min(floor(u[g] * n), n - 1) (the product in float) of az_pos_legal_indices' list
+ *   EXTERNAL  actions[g]: the seat of the reference's Player::Human or any caller-side bot
+ * The handle starts reset to the start position with cfg->seed. */
+int az_arena_create(const az_arena_player* p1, const az_arena_player* p2, const az_arena_cfg* cfg, int device,
+                    az_arena** out);
+int az_arena_destroy(az_arena* a);
+/* every game back to live with empty histories; start: [games] positions (each ongoing; its repetition
+ * multiset holds it once), NULL = the start position.  seed: the engine stream's.  Allocates nothing.
+ * With an MCTS player that does not play both sides, start positions that put one player to move in more
+ * than (games + 1) / 2 games at once are refused here (its search holds that many roots); nothing changes. */
+int az_arena_reset(az_arena* a, const az_pos* start, uint64_t seed);
+/* one ply of every live game.  u [games]: game g's uniform in [0,1) for this ply's move choice; NULL: the
+ * engine's stream, stream_key(seed, game, ply, 2).  actions [games]: read for games whose mover is
+ * AZ_PLAYER_EXTERNAL only (NULL with such a mover is an error).  *live = games still going after the ply.
+ * All or nothing: if an action is not a legal move index of its game, or a policy has a non-finite legal
+ * entry, the call fails with a message naming the game and no game has advanced. */
+int az_arena_step(az_arena* a, const float* u, const int32_t* actions, int* live);
+/* result[g]: AZ_ONGOING / AZ_DRAW / AZ_WHITE_WINS / AZ_BLACK_WINS; plies[g]: moves played (either may be NULL) */
+int az_arena_results(az_arena* a, int32_t* result, int32_t* plies);
+/* live[g] = 1 while game g is going, else 0, as the last az_arena_step (or reset) read it back: no device
+ * access.  Returns the number of live games. */
+int az_arena_live(az_arena* a, int32_t* live);
+/* the move indices of one game (at most cap written); returns the count */
+int az_arena_history(az_arena* a, int game, int32_t* moves, int cap);
+/* the two values validation.rs:209-254 accumulates, since the last reset */
+int az_arena_stats(az_arena* a, double* num_inferences, double* rows);
+/* validation.rs:297-308 / 337-350 over a 4096-entry policy (host, no device): fullmoves >
+ * num_stochastic_moves picks the LAST maximal index; else rand 0.8 WeightedIndex -- sequential f32
+ * cumulative sums, x = u * total (the largest float below total if that is not below it), the first index
+ * whose cumulative sum exceeds x, 4095 if none does */
+int az_arena_choose(const float* policy, int fullmoves, int num_stochastic_moves, float u);
+
 #ifdef __cplusplus
 }
 #endif
