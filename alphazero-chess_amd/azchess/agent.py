@@ -162,6 +162,11 @@ class AlphaZero:
         return L.check(L.lib.az_net_wino_accumulators(self._h))
 
     @property
+    def wino_v_rows(self):
+        """1 where the row-direct tower stores every row of its transformed input once (AZ_WINO_VROWS), else 0."""
+        return L.check(L.lib.az_net_wino_v_rows(self._h))
+
+    @property
     def winograd(self):
         return "Winograd" in self.tower_kernel
 
@@ -182,6 +187,15 @@ class AlphaZero:
         val = np.zeros(n, np.float32)
         L.check(L.lib.az_net_forward(self._h, L.fptr(x), n, L.fptr(pol), L.fptr(val)))
         return pol, val
+
+
+def wino_vrows_layout():
+    """az_wino_vrows_layout: the shared-row V layout's address tables (include/az.h), tabulated from the
+    kernel's own formulas; needs no device."""
+    t = dict(write=np.empty((16, 64, 4), np.int32), read=np.empty((2, 4, 4, 64), np.int32),
+             act=np.empty((16, 64, 4), np.int32), item=np.empty((2, 8, 4), np.int32), dims=np.empty(4, np.int32))
+    L.check(L.lib.az_wino_vrows_layout(*(t[k].ctypes.data_as(C.c_void_p) for k in ("write", "read", "act", "item", "dims"))))
+    return t
 
 
 def mx8_quantize(x):

@@ -23,6 +23,14 @@ static_assert(sizeof(azc::Pos) == sizeof(az_pos), "Pos == az_pos");
 #ifndef AZ_WINO_ROWS_DEFAULT
 #define AZ_WINO_ROWS_DEFAULT 1
 #endif
+#ifndef AZ_WINO_VROWS_DEFAULT
+#define AZ_WINO_VROWS_DEFAULT 1
+#endif
+// where the shared-row transform runs (wino.h wino_core_h16, VROWS): 0 waves 0-3 after their last step
+// of a chunk, 1 all eight waves inside the steps (A/B: DESIGN.md 5.4)
+#ifndef AZ_WINO_VROWS_SCHED
+#define AZ_WINO_VROWS_SCHED 0
+#endif
 // weight ring steps of the row-direct form (wino.h WinoRing; C3 A/B of 2, 3, 4: DESIGN.md 5.4)
 #ifndef AZ_WINO_ROWS_PF
 #define AZ_WINO_ROWS_PF 4
@@ -53,6 +61,11 @@ static inline int wino16_streamed(bool derive, int filters) { return derive && f
 constexpr int WINO_ROWS_PF = AZ_WINO_ROWS_PF;
 static_assert(12 % WINO_ROWS_PF == 0 && WINO_ROWS_PF >= 2, "the ring's slots must be compile-time");
 static inline bool wino16_rows(bool derive, bool rows, int filters) { return wino16_streamed(derive, filters) == 12 && rows; }
+// AZ_WINO_VROWS (default AZ_WINO_VROWS_DEFAULT): in the row-direct form, V holds every D row of the
+// padded board once (wino.h wino_vr_*: 10 rows x 4 column points, 20 KB per chunk) instead of the four
+// patch rows of every tile (32 KB: rows 2, 3 of a tile are rows 0, 1 of the tile below); the same bits
+// reach the same products.  Applies only where wino16_rows holds
+static inline bool wino16_vrows(bool rows_form, bool vrows) { return rows_form && vrows; }
 
 void set_error(const std::string& msg);
 int fail(const std::string& msg);
@@ -185,6 +198,8 @@ struct NetDev {
     int wino_streamed = 16;         // points per 32-channel group in wino16_w: 16, or 12 with row 2 derived
     bool wino_rows_env = AZ_WINO_ROWS_DEFAULT != 0;   // env AZ_WINO_ROWS=0/1 (wino16_rows)
     bool wino_rows = false;         // wino16_w holds the row-direct stream (winograd_split16_rows)
+    bool wino_vrows_env = AZ_WINO_VROWS_DEFAULT != 0;   // env AZ_WINO_VROWS=0/1 (wino16_vrows)
+    bool wino_vrows = false;        // the row-direct kernel keeps V in the shared-row layout
     float* head = nullptr;          // folded head weights (f32)
     void* head_frag = nullptr;      // 1x1 F->40 head conv as bf16 hi/lo MFMA A-fragments (fused tower)
     void* in_pk32 = nullptr;        // f32 Winograd nets: the input conv's weights with channels 16-18 of 4 taps packed per k-step (tower32w)

@@ -620,6 +620,7 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
     if (const char* e = getenv("AZ_WINO_SPLIT16")) net->split16 = atoi(e);
     if (const char* e = getenv("AZ_WINO_DERIVE")) net->wino_derive = atoi(e) != 0;
     if (const char* e = getenv("AZ_WINO_ROWS")) net->wino_rows_env = atoi(e) != 0;
+    if (const char* e = getenv("AZ_WINO_VROWS")) net->wino_vrows_env = atoi(e) != 0;
     AZ_HIP(hipStreamCreateWithFlags(&net->stream, hipStreamNonBlocking));
     const float* p = wts;
     std::vector<uint8_t> w8h, w8sh;      // fp8: the residual convs' fragments, scale bytes and biases, uploaded below
@@ -676,6 +677,7 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
             float us = 1.0f;
             net->wino_streamed = wino16_streamed(net->wino_derive, F);
             net->wino_rows = wino16_rows(net->wino_derive, net->wino_rows_env, F);
+            net->wino_vrows = wino16_vrows(net->wino_rows, net->wino_vrows_env);
             auto u = net->wino_rows ? winograd_split16_rows(wf.data(), F, &us)
                                     : winograd_split16(wf.data(), F, net->wino_streamed, &us);
             void* du = nullptr;

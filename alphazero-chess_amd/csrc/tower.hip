@@ -451,7 +451,7 @@ __device__ __forceinline__ unsigned long long* tt_slot(int w) {
 __device__ __forceinline__ unsigned long long* tt_slot(int) { return nullptr; }
 #endif
 
-template <int F, bool RESID, bool H16, int SP = 16, bool ROWS = false>
+template <int F, bool RESID, bool H16, int SP = 16, bool ROWS = false, bool VROWS = false>
 __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
                                           const __amdgpu_buffer_rsrc_t rW, const __amdgpu_buffer_rsrc_t rN,
                                           const float* __restrict__ bias, float unscale,
@@ -476,7 +476,7 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
     wino_stamp(tr, 0);
     // F = 64: the single chunk's V alternates between two buffers from conv to conv (vsel)
     const int vconv = vbase + (F == 64 ? vsel * VBYTES : 0);
-    if constexpr (H16) wino_core_h16<F, SP, ROWS>(ldsb, vconv, rW, rN, bias, unscale, wr, w, lane, y, pre_in, tr);
+    if constexpr (H16) wino_core_h16<F, SP, ROWS, VROWS>(ldsb, vconv, rW, rN, bias, unscale, wr, w, lane, y, pre_in, tr);
     else wino_core<F>(ldsb, vconv, rW, rN, bias, wr, w, lane, y, pre_in, tr);
     wino_stamp(tr, 10);
     f32x4 o[NN][4];
@@ -504,7 +504,9 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
             else
                 while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seq)
                     __builtin_amdgcn_s_sleep(1);
-            WinoXf<F>(ldsb, vbase, w, lane).template both<H16, ROWS ? WINO_XF_COLS : H16 && SP == 12 ? WINO_XF_NEG1 : WINO_XF_FULL>(0, 0);
+            // (shared rows: the same items as the tail transform, 4 per wave)
+            if constexpr (VROWS) WinoXf<F>(ldsb, vbase, w, lane).template vrows<WinoCfg<F>::NWV / 2>(0, 0);
+            else WinoXf<F>(ldsb, vbase, w, lane).template both<H16, ROWS ? WINO_XF_COLS : H16 && SP == 12 ? WINO_XF_NEG1 : WINO_XF_FULL>(0, 0);
         }
     } else if constexpr (F == 64) {
         // F = 64: each wave's 16 output channels are a quarter of the next conv's single chunk;
@@ -521,7 +523,7 @@ __device__ __forceinline__ void conv_wino(char* __restrict__ ldsb, int vbase,
 
 // one board (batch row row0) through the Winograd f32 tower, all NWV waves of the workgroup; SP: the
 // split-f16 weights' streamed points per 32-channel group (wino_core_h16)
-template <int F, bool SEARCH, bool H16, int SP = 16, bool ROWS = false>
+template <int F, bool SEARCH, bool H16, int SP = 16, bool ROWS = false, bool VROWS = false>
 __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes, const TowerArgs& ta, int row0,
                                                       float* __restrict__ pol_out, float* __restrict__ val_out,
                                                       const SearchOut& so, int tid) {
@@ -531,7 +533,8 @@ __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes,
     constexpr int XSZ = 64 * RSF;                        // ACT, uint4 slots
     // both V buffers (one when a single chunk covers the input), also planes staging / heads scratch
     // (F = 64: two single-chunk buffers, alternating from conv to conv)
-    constexpr int VSZ = (F / WinoCfg<F>::CH > 1 || F == 64 ? 2 : 1) * WinoCfg<F>::CH * 1024 / 16;
+    // (shared rows: two buffers of WINO_VR_BYTES, 40 KB instead of 64)
+    constexpr int VSZ = VROWS ? 2 * WINO_VR_BYTES / 16 : (F / WinoCfg<F>::CH > 1 || F == 64 ? 2 : 1) * WinoCfg<F>::CH * 1024 / 16;
     constexpr int PF = WinoRing<F, H16, ROWS>::PF;
     constexpr int ZN = 16 + F / 4;
     constexpr int PAD = WINO_PAD_SQ * RSF;               // zero squares either side of ACT
@@ -572,6 +575,13 @@ __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes,
                                                          r0, voff + n * 1024 + i * (F / 16) * 1024, 0, 0));
         conv32_in_packed<F, RSI, RSF, NN>(ldsb, reinterpret_cast<char*>(X), vbase, zero_off, r0, ta.b[0], wr, w, lane);
     }
+    if constexpr (VROWS) {
+        // the planes staged in V are consumed (the input conv ends in a barrier): zero the off-board rows 0
+        // and 9 of both buffers' planes, 32 runs of 256 B, one uint4 per thread; no item writes them, and
+        // the chunk-0 transform's barrier publishes them before the first B read
+        static_assert(NT == 32 * 16, "one uint4 of the zero rows per thread");
+        *reinterpret_cast<uint4*>(ldsb + vbase + wino_vr_zero(tid >> 4) + (tid & 15) * 16) = make_uint4(0, 0, 0, 0);
+    }
     wino_stamp(tr, 2);
     f32x4 xres[NN][4];
     f32x4 wring[PF][RX][NN];
@@ -599,9 +609,9 @@ __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes,
         // F = 256 / 64: each conv transforms the next conv's chunk 0 at its end (conv_wino; C3 A/B
         // -0.3 % against the tail transform alone)
         constexpr bool PRE = F == 256 || F == 64;
-        conv_wino<F, false, H16, SP, ROWS>(ldsb, vbase, r1, r2, ta.b[1 + 2 * b], ta.wus[2 * b], wring, xres, w, lane, PRE && b > 0, PRE, 0, flag,
+        conv_wino<F, false, H16, SP, ROWS, VROWS>(ldsb, vbase, r1, r2, ta.b[1 + 2 * b], ta.wus[2 * b], wring, xres, w, lane, PRE && b > 0, PRE, 0, flag,
                             2 * b + 1, tr ? tr + 3 + 64 * b : nullptr);
-        conv_wino<F, true, H16, SP, ROWS>(ldsb, vbase, r2, r3, ta.b[2 + 2 * b], ta.wus[2 * b + 1], wring, xres, w, lane, PRE, PRE && b + 1 < ta.blocks,
+        conv_wino<F, true, H16, SP, ROWS, VROWS>(ldsb, vbase, r2, r3, ta.b[2 + 2 * b], ta.wus[2 * b + 1], wring, xres, w, lane, PRE, PRE && b + 1 < ta.blocks,
                            F == 64 ? 1 : 0, flag, 2 * b + 2, tr ? tr + 35 + 64 * b : nullptr);
     }
     heads_group<F, RSF, 1, NT, SEARCH, true, H16>(ldsb, reinterpret_cast<float*>(V), 0, 1, row0, tid, ta.head_frag32, ta.head,
@@ -609,13 +619,13 @@ __device__ __forceinline__ void tower32w_board(const float* __restrict__ planes,
     wino_stamp(tr, 3 + 64 * 20);
 }
 
-template <int F, bool SEARCH, bool H16, int SP = 16, bool ROWS = false>
+template <int F, bool SEARCH, bool H16, int SP = 16, bool ROWS = false, bool VROWS = false>
 __global__ void __launch_bounds__(WinoCfg<F>::NWV * 64)
 tower32w_kernel(const float* __restrict__ planes, TowerArgs ta, const int* __restrict__ count_ptr, int rows,
                 float* __restrict__ pol_out, float* __restrict__ val_out, SearchOut so) {
     const int count = count_ptr ? min(load_fresh(count_ptr), rows) : rows;
     if ((int)blockIdx.x >= count) return;
-    tower32w_board<F, SEARCH, H16, SP, ROWS>(planes, ta, blockIdx.x, pol_out, val_out, so, threadIdx.x);
+    tower32w_board<F, SEARCH, H16, SP, ROWS, VROWS>(planes, ta, blockIdx.x, pol_out, val_out, so, threadIdx.x);
 }
 
 // k_sims32w: simulation steps [step0, step1) of one game per workgroup, with no grid-wide step
@@ -635,7 +645,7 @@ template <int F> struct SimsCfg<F, true> {
     static_assert(TowerCfg<F>::BPB == 1, "persistent bf16 kernel: one board per workgroup");
     static constexpr int NT = (F / (16 * TowerCfg<F>::NCO)) * TowerCfg<F>::WB * 64;
 };
-template <int F, bool BF16, bool H16 = false, int SP = 16, bool ROWS = false>
+template <int F, bool BF16, bool H16 = false, int SP = 16, bool ROWS = false, bool VROWS = false>
 __global__ void __launch_bounds__((SimsCfg<F, BF16>::NT))
 k_sims32w(Engine E, TowerArgs ta, SearchOut so, int step0, int step1) {
     __shared__ int s_kind;
@@ -683,7 +693,7 @@ k_sims32w(Engine E, TowerArgs ta, SearchOut so, int step0, int step1) {
         wino_stamp(tr, 1914);
         if (kind == X_ROW) {
             if constexpr (BF16) tower_board<F, true>(nullptr, ta, g, 1, nullptr, nullptr, so, tid);
-            else tower32w_board<F, true, H16, SP, ROWS>(nullptr, ta, g, nullptr, nullptr, so, tid);
+            else tower32w_board<F, true, H16, SP, ROWS, VROWS>(nullptr, ta, g, nullptr, nullptr, so, tid);
         }
         __syncthreads();
         wino_stamp(tr, 1915);
@@ -745,17 +755,18 @@ int sims_persistent(const NetDev* n, const Engine& E, const SearchOut& so, int s
         k_sims32w<64, true><<<E.G, SimsCfg<64, true>::NT, 0, st>>>(E, ta, so, step0, step1);
         return hipGetLastError() == hipSuccess ? 0 : fail("persistent simulation kernel launch failed");
     }
-#define AZ_SIMS32W(FF, H16, SP, ROWS)                                                                        \
+#define AZ_SIMS32W(FF, H16, SP, ROWS, VR)                                                                   \
     if (n->filters == FF) {                                                                            \
-        k_sims32w<FF, false, H16, SP, ROWS><<<E.G, SimsCfg<FF, false>::NT, 0, st>>>(E, ta, so, step0, step1); \
+        k_sims32w<FF, false, H16, SP, ROWS, VR><<<E.G, SimsCfg<FF, false>::NT, 0, st>>>(E, ta, so, step0, step1); \
         return hipGetLastError() == hipSuccess ? 0 : fail("persistent simulation kernel launch failed"); \
     }
     if (wino_split16(n)) {
-        if (n->wino_streamed == 12 && n->wino_rows) { AZ_SIMS32W(256, true, 12, true) }
-        if (n->wino_streamed == 12) { AZ_SIMS32W(256, true, 12, false) }
-        AZ_SIMS32W(256, true, 16, false) AZ_SIMS32W(128, true, 16, false) AZ_SIMS32W(64, true, 16, false)
+        if (n->wino_streamed == 12 && n->wino_rows && n->wino_vrows) { AZ_SIMS32W(256, true, 12, true, true) }
+        if (n->wino_streamed == 12 && n->wino_rows) { AZ_SIMS32W(256, true, 12, true, false) }
+        if (n->wino_streamed == 12) { AZ_SIMS32W(256, true, 12, false, false) }
+        AZ_SIMS32W(256, true, 16, false, false) AZ_SIMS32W(128, true, 16, false, false) AZ_SIMS32W(64, true, 16, false, false)
     }
-    AZ_SIMS32W(256, false, 16, false) AZ_SIMS32W(128, false, 16, false) AZ_SIMS32W(64, false, 16, false)
+    AZ_SIMS32W(256, false, 16, false, false) AZ_SIMS32W(128, false, 16, false, false) AZ_SIMS32W(64, false, 16, false, false)
 #undef AZ_SIMS32W
     return fail("persistent simulation kernel: unsupported filters");
 }
@@ -789,20 +800,21 @@ int tower_forward(NetDev* n, const void* planes, const int* count, int rows, flo
         return hipGetLastError() == hipSuccess ? 0 : fail("f32 tower launch failed");                          \
     }
     if (n->dtype == AZ_DTYPE_F32) {
-#define AZ_TOWER32W(FF, H16, SP, ROWS)                                                                         \
+#define AZ_TOWER32W(FF, H16, SP, ROWS, VR)                                                                       \
         if (n->filters == FF) {                                                                                \
             constexpr int NT = WinoCfg<FF>::NWV * 64;                                                          \
-            if (so) tower32w_kernel<FF, true, H16, SP, ROWS><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s); \
-            else tower32w_kernel<FF, false, H16, SP, ROWS><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s);  \
+            if (so) tower32w_kernel<FF, true, H16, SP, ROWS, VR><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s); \
+            else tower32w_kernel<FF, false, H16, SP, ROWS, VR><<<rows, NT, 0, st>>>((const float*)planes, ta, count, rows, pol, val, s);  \
             return hipGetLastError() == hipSuccess ? 0 : fail("f32 Winograd tower launch failed");             \
         }
         if (wino_split16(n)) {
-            if (n->wino_streamed == 12 && n->wino_rows) { AZ_TOWER32W(256, true, 12, true) }
-            if (n->wino_streamed == 12) { AZ_TOWER32W(256, true, 12, false) }
-            AZ_TOWER32W(256, true, 16, false) AZ_TOWER32W(128, true, 16, false) AZ_TOWER32W(64, true, 16, false)
+            if (n->wino_streamed == 12 && n->wino_rows && n->wino_vrows) { AZ_TOWER32W(256, true, 12, true, true) }
+            if (n->wino_streamed == 12 && n->wino_rows) { AZ_TOWER32W(256, true, 12, true, false) }
+            if (n->wino_streamed == 12) { AZ_TOWER32W(256, true, 12, false, false) }
+            AZ_TOWER32W(256, true, 16, false, false) AZ_TOWER32W(128, true, 16, false, false) AZ_TOWER32W(64, true, 16, false, false)
         }
         if (wino_supported(n)) {
-            AZ_TOWER32W(256, false, 16, false) AZ_TOWER32W(128, false, 16, false) AZ_TOWER32W(64, false, 16, false)
+            AZ_TOWER32W(256, false, 16, false, false) AZ_TOWER32W(128, false, 16, false, false) AZ_TOWER32W(64, false, 16, false, false)
         }
 #undef AZ_TOWER32W
         AZ_TOWER32(256) AZ_TOWER32(128) AZ_TOWER32(64) AZ_TOWER32(32)
@@ -815,6 +827,32 @@ int tower_forward(NetDev* n, const void* planes, const int* count, int rows, flo
 }
 
 }  // namespace azi
+
+// the shared-row V layout's address functions (wino.h wino_vr_*), tabulated on the host (include/az.h)
+extern "C" int az_wino_vrows_layout(int* write, int* read, int* act, int* item, int* dims) {
+    using namespace azi;
+    if (!write || !read || !act || !item || !dims) return fail("null argument");
+    for (int q = 0; q < WINO_VR_ITEMS; q++)
+        for (int lane = 0; lane < 64; lane++)
+            for (int k = 0; k < 4; k++) {
+                write[(q * 64 + lane) * 4 + k] = wino_vr_write(q, lane, k);
+                act[(q * 64 + lane) * 4 + k] = wino_vr_act(q, lane, k);
+            }
+    for (int i = 0; i < 4; i++)
+        for (int b = 0; b < 4; b++)
+            for (int lane = 0; lane < 64; lane++) {
+                read[(i * 4 + b) * 64 + lane] = wino_vr_read(i, b, lane);
+                read[((4 + i) * 4 + b) * 64 + lane] = wino_vr_lo(wino_vr_rlane(lane, i >> 1)) + wino_vr_rimm(i, b);
+            }
+    for (int sched = 0; sched < 2; sched++)
+        for (int wave = 0; wave < 8; wave++)
+            for (int it = 0; it < 4; it++) {
+                const int nw = sched ? 8 : 4;
+                item[(sched * 8 + wave) * 4 + it] = wave < nw && it < WINO_VR_ITEMS / nw ? wino_vr_item(wave, it, nw) : -1;
+            }
+    dims[0] = WINO_VR_PLANE; dims[1] = WINO_VR_BYTES; dims[2] = WINO_VR_R16; dims[3] = 4;
+    return 0;
+}
 
 #ifdef AZ_TOWER_TRACE
 // trace build only: copy the phase stamps of the last tower launch (AZ_TT_WG x 8 waves x

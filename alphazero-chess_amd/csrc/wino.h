@@ -144,6 +144,67 @@ template <int F> __device__ __forceinline__ int wino16_voff(int w, int lane) {
 // keeps the 32-lane groups of each read on distinct banks) and multiplied by 0 in store.
 // the input transform's forms (WinoXf::store16)
 constexpr int WINO_XF_FULL = 0, WINO_XF_NEG1 = 1, WINO_XF_COLS = 2;
+
+// ---- V with shared rows (the row-direct form at F = 256, AZ_WINO_VROWS).  Rows 2, 3 of a tile's patch
+// are rows 0, 1 of the tile below, so the per-tile V holds every D row of board rows 1-6 twice and the
+// rows off the board as computed zeros.  Here a chunk's V holds each D row of the padded board once:
+// entry (column point b, padded row r = 0..9, channel octet o, tile column tc) = 8 channels of f16,
+// 16 B, in a hi plane and a lo plane of 640 entries (VR_PLANE = 10 KB; a buffer 20 KB against 32; the lo
+// plane with the tile column ^ 2: wino_vr_lo).  Rows
+// 0 and 9 are off the board: zeroed once per board (tower32w_board), never written by an item.
+//   entry address  ((2 b + (r & 1)) 5 + (r >> 1)) 256 + (4 (o ^ 2 ((r >> 1) & 1)) + tc) 16
+// The B fragment of patch row i, point b of lane (h = lane >> 4, tr = (lane & 15) >> 2, tc = lane & 3) is
+// entry (b, 2 tr + i, h, tc), one ds_read_b128 per plane: the eight (h, tr) of a ds_read_b128 lane group
+// fall on four distinct octet slots (the XOR by the row pair's parity), 64 banks, one-way.
+// Transform items: one lane = one channel x one board row x one tile column; a wave-item q = 0..15 is
+// row 1 + (q >> 1), channels 16 (q & 1) + (lane & 15) of the chunk, tile column lane >> 4.  4 ACT reads
+// (columns 2 tc - 1 .. 2 tc + 2, clamped as WinoXf::load), the 4 points of xform_cols, 4 x split16, pair
+// swap, 4 ds_write_b32 (32 lanes = 2 octets x 2 tile columns x 4 pairs x hi, lo: 32 banks).  The
+// arithmetic per entry is xform_cols' and split16's: every stored bit is the per-tile form's.
+// The address functions are host-callable: az_wino_vrows_layout tabulates them for tests/.
+constexpr int WINO_VR_PLANE = 10240, WINO_VR_BYTES = 2 * WINO_VR_PLANE, WINO_VR_ITEMS = 16;
+constexpr int WINO_VR_R16 = (256 / 4 + 2) * 16;                     // ACT square stride at F = 256
+// the lo plane's copy of a hi-plane address (its part below 256 B): one plane further, tile column ^ 2 --
+// the hi and the lo lane of a channel pair then write 8 banks apart (on one bank the ds_write_b32 was
+// 2-way: SQ_LDS_BANK_CONFLICT 1.6x the per-tile form's); uniform within a read
+__host__ __device__ constexpr int wino_vr_lo(int a) { return (a ^ 32) + WINO_VR_PLANE; }
+__host__ __device__ constexpr int wino_vr_lo_if(int lo, int a) { return lo ? wino_vr_lo(a) : a; }
+__host__ __device__ constexpr int wino_vr_item(int wave, int it, int nw) { return wave + nw * it; }   // nw transform waves
+__host__ __device__ constexpr int wino_vr_item_row(int q) { return 1 + (q >> 1); }
+// write address of (wave-item q, lane, point b) = the item's wave-uniform part + the lane's + b's
+__host__ __device__ constexpr int wino_vr_wuni(int q) {
+    const int r = wino_vr_item_row(q), rp = (r >> 1) & 1;
+    return ((r & 1) * 5 + (r >> 1)) * 256 + (((q & 1) ^ rp) * 2) * 64;
+}
+__host__ __device__ constexpr int wino_vr_wlane(int lane) {
+    return wino_vr_lo_if(lane & 1, ((lane >> 3) & 1) * 64 + (lane >> 4) * 16) + ((lane & 7) >> 1) * 4;
+}
+__host__ __device__ constexpr int wino_vr_wpoint(int b) { return b * 2560; }
+__host__ __device__ constexpr int wino_vr_write(int q, int lane, int b) { return wino_vr_wuni(q) + wino_vr_wlane(lane) + wino_vr_wpoint(b); }
+// read address (hi plane; lo: wino_vr_lo of the lane's part) of patch row i, point b: the lane's part for the row pair
+// i >> 1 + an immediate
+// (the next row pair is one 256-byte run further, and its parity flips the octet slot's bit 1: byte 128)
+__host__ __device__ constexpr int wino_vr_rlane(int lane, int i2) {
+    const int h = lane >> 4, tr = (lane & 15) >> 2, tc = lane & 3;
+    const int a0 = tr * 256 + (4 * (h ^ (2 * (tr & 1))) + tc) * 16;
+    return i2 ? (a0 ^ 128) + 256 : a0;
+}
+__host__ __device__ constexpr int wino_vr_rimm(int i, int b) { return (2 * b + (i & 1)) * 5 * 256; }
+__host__ __device__ constexpr int wino_vr_read(int i, int b, int lane) { return wino_vr_rlane(lane, i >> 1) + wino_vr_rimm(i, b); }
+// the 32 runs of 256 B that are rows 0 and 9 (k = 16 buffer + 8 plane + 2 b + (0: row 0, 1: row 9)), bytes
+// from the first buffer
+__host__ __device__ constexpr int wino_vr_zero(int k) {
+    return (k >> 4) * WINO_VR_BYTES + ((k >> 3) & 1) * WINO_VR_PLANE + (k & 1 ? (2 * ((k >> 1) & 3) + 1) * 5 + 4 : 2 * ((k >> 1) & 3) * 5) * 256;
+}
+// the item's ACT reads (bytes from ACT, chunk 0): column j of row r - 1, channel 16 (q & 1) + (lane & 15);
+// lane part (column 2 tc), the clamped steps to columns j = 0 and 3, the wave-uniform part
+__host__ __device__ constexpr int wino_vr_alane(int lane) { return (lane >> 4) * (2 * WINO_VR_R16) + (lane & 15) * 4; }
+__host__ __device__ constexpr int wino_vr_acol(int tc, int j) {
+    return j == 0 ? (tc > 0 ? -WINO_VR_R16 : 3 * WINO_VR_R16) : j == 1 ? 0 : j == 2 ? WINO_VR_R16
+                                                                  : (tc < 3 ? 2 * WINO_VR_R16 : -2 * WINO_VR_R16);
+}
+__host__ __device__ constexpr int wino_vr_auni(int q) { return (wino_vr_item_row(q) - 1) * 8 * WINO_VR_R16 + (q & 1) * 64; }
+__host__ __device__ constexpr int wino_vr_act(int q, int lane, int j) { return wino_vr_auni(q) + wino_vr_alane(lane) + wino_vr_acol(lane >> 4, j); }
 template <int F> struct WinoXf {
     static constexpr int NWV = WinoCfg<F>::NWV, CH = WinoCfg<F>::CH, RS = F / 4 + 2;
     static constexpr int VBYTES = CH * 1024, XST = CH * 64, IT = CH * 16 / (NWV * 64);
@@ -295,6 +356,46 @@ template <int F> struct WinoXf {
                         const unsigned oth = (unsigned)__builtin_amdgcn_update_dpp(0, (int)own, 0xB1, 0xF, 0xF, true);
                         *reinterpret_cast<unsigned*>(vb + ((2 * rp + e) * 4 + k) * XST16) = __builtin_amdgcn_perm(oth, own, sel);
                     }
+        }
+    }
+    // ---- shared-row items (wino_vr_* above, F = 256): vr_load issues wave-item q's four ACT reads of
+    // chunk c, vr_store makes the four points with xform_cols' operations (each multiply by 1 or 0 inside
+    // an FMA, the same roundings), splits, swaps within the channel pair and writes them into V[buf]
+    // (ln: the lane index laundered by the caller, so that nothing derived from it stays live from chunk
+    // to chunk: see load)
+    __device__ __forceinline__ void vr_load(int c, int q, float (&e)[4], int ln) const {
+        static_assert(F == 256 && R16 == WINO_VR_R16 && CH == 32, "the shared-row layout is the 256-filter tower's");
+        const int tl = ln >> 4;
+        const char* p = ldsb + wino_vr_alane(ln) + wino_vr_auni(q) + c * CH * 4;
+#pragma unroll
+        for (int j = 0; j < 4; j++) e[j] = *reinterpret_cast<const float*>(p + wino_vr_acol(tl, j));
+    }
+    __device__ __forceinline__ void vr_store(int buf, int q, const float (&e)[4], int ln) const {
+        const int tl = ln >> 4;
+        const float m0 = tl > 0 ? 1.0f : 0.0f, m3 = tl < 3 ? 1.0f : 0.0f;
+        const unsigned sel = (ln & 1) ? 0x03020706u : 0x05040100u;
+        const float v[4] = {__builtin_fmaf(e[0], m0, -e[2]), e[1] + e[2], e[2] - e[1], __builtin_fmaf(-e[3], m3, e[1])};
+        char* vb = ldsb + vbase + buf * WINO_VR_BYTES + wino_vr_wuni(q) + wino_vr_wlane(ln);
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const unsigned own = split16(v[b]);
+            const unsigned oth = (unsigned)__builtin_amdgcn_update_dpp(0, (int)own, 0xB1, 0xF, 0xF, true);
+            *reinterpret_cast<unsigned*>(vb + wino_vr_wpoint(b)) = __builtin_amdgcn_perm(oth, own, sel);
+        }
+    }
+    // chunk c into V[buf] by the first NW waves, WINO_VR_ITEMS / NW wave-items each
+    template <int NW> __device__ __forceinline__ void vrows(int c, int buf) const {
+        // two items' reads in flight at a time: 8 VGPRs of patch values
+        constexpr int NI = WINO_VR_ITEMS / NW;
+        static_assert(NI % 2 == 0, "items in pairs");
+        const int ln = vgpr_index(lane);
+#pragma unroll
+        for (int i2 = 0; i2 < NI; i2 += 2) {
+            float e[2][4];
+            vr_load(c, wino_vr_item(w, i2, NW), e[0], ln);
+            vr_load(c, wino_vr_item(w, i2 + 1, NW), e[1], ln);
+            vr_store(buf, wino_vr_item(w, i2, NW), e[0], ln);
+            vr_store(buf, wino_vr_item(w, i2 + 1, NW), e[1], ln);
         }
     }
 };
@@ -629,7 +730,15 @@ __device__ __forceinline__ void wino_core(char* __restrict__ ldsb, int vbase,
 //            negated), 16 V planes (4 i + b) and 12 MFMAs per step in four chains as the derived form;
 //            the input transform loses its row pass, the output transform its first stage, and no
 //            product is derived.  The registers that frees hold a deeper ring (WinoRing).
-template <int F, int SP = 16, bool ROWS = false>
+//   VROWS    (ROWS, AZ_WINO_VROWS) V holds every D row of the padded board once (wino_vr_* above: 20 KB per
+//            chunk instead of 32) instead of the four patch rows of every tile; the transform is 16 small
+//            wave-items per chunk (WinoXf::vrows) and does half the arithmetic and LDS writes.  The B
+//            fragment of (patch row i, point b) is entry (b, 2 tr + i, h, tc): the same bits into the same
+//            MFMAs.  The phase trace put the tail transform of waves 0-3 on the chunk's
+//            critical path -- they request no weights while they transform and are last at every chunk
+//            barrier -- so it stays where it was and gets shorter (AZ_WINO_VROWS_SCHED 0); spreading it
+//            over all eight waves inside the steps (1) measured slower: it loads the late waves.
+template <int F, int SP = 16, bool ROWS = false, bool VROWS = false>
 __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase,
                                               const __amdgpu_buffer_rsrc_t rW, const __amdgpu_buffer_rsrc_t rN,
                                               const float* __restrict__ bias, float unscale,
@@ -643,6 +752,8 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
     constexpr bool DER = SP == 12 && !ROWS;
     static_assert(SP == 16 || (SP == 12 && XS == 1 && CH == 32), "12 streamed planes: one per step, one group per chunk");
     static_assert(!ROWS || (SP == 12 && F == 256), "the row-direct form: 256 filters, 12 streamed planes");
+    static_assert(!VROWS || ROWS, "shared V rows: the row-direct form only");
+    constexpr bool VSTEPS = VROWS && AZ_WINO_VROWS_SCHED == 1;       // the transform inside the steps, all waves
     constexpr int NACC = ROWS ? 8 : 16;
     constexpr int XFORM = ROWS ? WINO_XF_COLS : DER ? WINO_XF_NEG1 : WINO_XF_FULL;
     constexpr int VBYTES = CH * 1024, NCHUNK = F / CH, SPC = (CH / 32) * 16, SPX = SP == 12 ? 12 : SPC / XS;
@@ -657,6 +768,9 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
     const int l16 = lane & 15, h = lane >> 4;
     const int vrd = h * 256 + ((l16 ^ (2 * h)) * 16);                // hi plane; lo: slot ^ 4, + VBYTES / 2
     const int vrl = VBYTES / 2 + h * 256 + ((l16 ^ (2 * h) ^ 4) * 16);
+    // shared rows: the lane's part of the read address for patch rows 0, 1 (vrd) and 2, 3 (vrl), hi plane
+    const int vr0 = VROWS ? wino_vr_rlane(lane, 0) : vrd, vr1 = VROWS ? wino_vr_rlane(lane, 1) : vrl;   // vr1 = (vr0 ^ 128) + 256
+    constexpr int VBUF = VROWS ? WINO_VR_BYTES : VBYTES;             // bytes of a chunk's V buffer
     const WinoXf<F> xf(ldsb, vbase, w, lane);
     const int co0 = w * 16 * NN + h * 4;
     f32x4 acc[NACC][NN];
@@ -675,9 +789,13 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
         }
     const int voff = wino16_voff<F>(w, lane);
     if (!pre) {   // chunk 0 not transformed by the caller
-        typename WinoXf<F>::Patch d0;
-        xf.load(0, d0);
-        xf.template store16<XFORM>(0, d0);
+        if constexpr (VROWS) {
+            xf.template vrows<NWV>(0, 0);
+        } else {
+            typename WinoXf<F>::Patch d0;
+            xf.load(0, d0);
+            xf.template store16<XFORM>(0, d0);
+        }
         __syncthreads();
     }
     wino_stamp(tr, 1);
@@ -689,7 +807,7 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
 #pragma unroll 1
     for (int c = 0; c < NCHUNK; c++) {
         typename WinoXf<F>::Patch dn;
-        const int vb = vbase + (c & 1) * VBYTES;
+        const int vb = vbase + (c & 1) * VBUF;
         const bool more = c + 1 < NCHUNK;
         if constexpr (ROWS) {
             // row-direct form.  B fragments: a rolling window of three planes, numbered n = 4 b + i in the
@@ -699,10 +817,18 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
             // just freed: 24 VGPRs, every read at least a step ahead of its use
             (void)dn;
             f16x8 bw[3][2];
+            float en[2][4];                                          // VSTEPS: the wave's two items of chunk c + 1
             auto bread = [&](int n) {
-                const int pt = 4 * (n % 4) + n / 4;
-                bw[n % 3][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + pt * XST16);
-                bw[n % 3][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + pt * XST16);
+                if constexpr (VROWS) {   // patch row n % 4 of point n / 4: entry (b, 2 tr + i, h, tc)
+                    const int vl = (n % 4) >> 1 ? vr1 : vr0;
+                    const char* p = ldsb + vb + wino_vr_rimm(n % 4, n / 4);
+                    bw[n % 3][0] = *reinterpret_cast<const f16x8*>(p + vl);
+                    bw[n % 3][1] = *reinterpret_cast<const f16x8*>(p + wino_vr_lo(vl));
+                } else {
+                    const int pt = 4 * (n % 4) + n / 4;
+                    bw[n % 3][0] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrd + pt * XST16);
+                    bw[n % 3][1] = *reinterpret_cast<const f16x8*>(ldsb + vb + vrl + pt * XST16);
+                }
             };
             bread(0);
             bread(1);
@@ -744,8 +870,30 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
                 __builtin_amdgcn_sched_barrier(0);
                 if (st % 3 == 2 && st + 1 < SPX) bread(n0 + 3);
                 if (st == 4) wino_stamp(tr, 20 + c);
-                // the next chunk's transform: as in wino_core, by the first wave of each SIMD pair
-                if (st == SPX - 1 && more && w < NWV / 2) xf.template both<true, XFORM>(c + 1, (c + 1) & 1);
+                // the next chunk's transform: as in wino_core, by the first wave of each SIMD pair; shared rows:
+                // the same (AZ_WINO_VROWS_SCHED 0: 4 items per wave), or every wave's two items inside the steps,
+                // reads two steps ahead of the transform and writes (1), so that no wave stops requesting
+                // weights; V[(c + 1) & 1] is free since the previous chunk's barrier
+                if constexpr (VSTEPS) {
+                    if (more) {
+                        if (st == 1) xf.vr_load(c + 1, wino_vr_item(w, 0, NWV), en[0], vgpr_index(lane));
+                        if (st == 3) xf.vr_store((c + 1) & 1, wino_vr_item(w, 0, NWV), en[0], vgpr_index(lane));
+                        if (st == 5) xf.vr_load(c + 1, wino_vr_item(w, 1, NWV), en[1], vgpr_index(lane));
+                        if (st == 7) xf.vr_store((c + 1) & 1, wino_vr_item(w, 1, NWV), en[1], vgpr_index(lane));
+                    }
+                } else if constexpr (VROWS) {
+                    (void)en;
+                    if (st == SPX - 1 && more && w < NWV / 2) {
+                        if (c < 4) wino_stamp(tr, 28 + c);   // start of the tail transform (chunks 0-3: the free slots)
+                        xf.template vrows<NWV / 2>(c + 1, (c + 1) & 1);
+                    }
+                } else {
+                    (void)en;
+                    if (st == SPX - 1 && more && w < NWV / 2) {
+                        if (c < 4) wino_stamp(tr, 28 + c);
+                        xf.template both<true, XFORM>(c + 1, (c + 1) & 1);
+                    }
+                }
             }
         } else {
             f16x8 bq[LA][XS][2];

@@ -98,6 +98,17 @@ int az_net_wino_streamed_points(az_net* net);
  * or derived), or 8 where the kernel is Winograd across columns only and sums the three tap rows
  * directly (AZ_WINO_ROWS, 256 filters, 12 streamed planes); 0 for a net that another kernel evaluates */
 int az_net_wino_accumulators(az_net* net);
+/* 1 where the row-direct split-f16 tower keeps its transformed input with every row of the padded board
+ * stored once (AZ_WINO_VROWS, only where az_net_wino_accumulators is 8), 0 otherwise */
+int az_net_wino_v_rows(az_net* net);
+/* The shared-row V layout's address functions, tabulated from the formulas the kernel uses (wino.h
+ * wino_vr_*), byte offsets: write[q][lane][b] of wave-item q (16 per chunk), point b within a chunk's V
+ * buffer (16 x 64 x 4); read[plane][i][b][lane] of patch row i, point b in the hi and the lo plane
+ * (2 x 4 x 4 x 64); act[q][lane][j] of the item's read of column j within the layer input (16 x 64 x 4,
+ * chunk 0); item[sched][wave][it]
+ * the wave-item of transform wave `wave`, or -1 (2 x 8 x 4: sched 0 waves 0-3 x 4 items, 1 eight waves
+ * x 2); dims = {plane bytes, buffer bytes, ACT square stride, ACT channel bytes}.  Needs no device. */
+int az_wino_vrows_layout(int* write, int* read, int* act, int* item, int* dims);
 /* burn NamedMpkFileRecorder<FullPrecisionSettings> model files:
  * load_model (main.rs:109-116) -> flat weights for az_net_create / az_trainer_create, and
  * model.save_file (training.rs:269-270) from flat weights.  out/w hold az_net_num_params floats. */

@@ -2,7 +2,8 @@
 per phase of tower32w_board, mean over the traced workgroups' waves and the 2B residual convs.
 Slots per wave: 0 start, 1 planes staged, 2 input conv done, conv i at 3 + 32 i: +0 start, +1 chunk-0
 transform barrier, +2+c after chunk c's barrier, +10 core done (before the epilogue), +11 epilogue
-written, +12+c before chunk c's barrier, +20+c after step 4 of chunk c; 3 + 64 B: heads done.
+written, +12+c before chunk c's barrier, +20+c after step 4 of chunk c, +28+c (c < 4, waves 0-3 of the
+256-filter row-direct forms) start of the tail transform of chunk c + 1; 3 + 64 B: heads done.
 Usage: python tools/tower_trace.py trace.bin [blocks]"""
 import sys
 
@@ -40,3 +41,21 @@ print("mean chunk (barrier to barrier) %.0f cycles; MFMA work per SIMD per chunk
 sk = conv.max(1) - conv.min(1)
 print("wave skew within a workgroup (max - min), mean: start %.0f, after chunk barriers %.0f, before chunk barriers %.0f, after step 4 %.0f"
       % (sk[..., 0].mean(), sk[..., 2:10].mean(), sk[..., 12:20].mean(), sk[..., 20:28].mean()))
+# the tail transform, the barrier waits of the two halves and the conv boundary (256-filter row-direct forms)
+early, latew = conv[:, :4], conv[:, 4:]
+if (early[..., 28:32] > 0).all():
+    tail = early[..., 12:16] - early[..., 28:32]
+    print("tail transform, waves 0-3, chunks 0-3: mean %.0f  min %.0f  max %.0f cycles" % (tail.mean(), tail.min(), tail.max()))
+    lead = latew[..., 12:16].max(1, keepdims=True) - early[..., 28:32]
+    print("last late wave's arrival at the barrier minus tail start: mean %.0f" % lead.mean())
+else:
+    print("no tail stamps (transform inside the steps, or another form)")
+for name, x in (("waves 0-3", early), ("waves 4-7", latew)):
+    print("barrier wait %s (chunks 0-6): mean %.0f" % (name, (x[..., 2:9] - x[..., 12:19]).mean()))
+arr = conv[..., 12:19]                                # arrival at the chunk barrier [wg, wave, conv, 7]
+print("last arrival at the chunk barrier is a wave 0-3 in %.0f %% of chunks" % (100.0 * (arr == arr.max(1, keepdims=True))[:, :4].any(1).mean()))
+print("slack of the other half at the barrier: waves 0-3 arrive %.0f cycles after the last of waves 4-7 (negative: before)"
+      % (arr[:, :4].max(1) - arr[:, 4:].max(1)).mean())
+bd = conv[:, :, 1:, 1] - conv[:, :, :-1, 19]
+print("conv boundary (chunk 7 done -> next conv's chunk loop): mean %.0f, waves 0-3 %.0f, waves 4-7 %.0f"
+      % (bd.mean(), bd[:, :4].mean(), bd[:, 4:].mean()))
