@@ -116,6 +116,8 @@ SIGNATURES = [
     ("az_net_wino_accumulators", C.c_int, [C.c_void_p]),
     ("az_net_wino_v_rows", C.c_int, [C.c_void_p]),
     ("az_wino_vrows_layout", C.c_int, [C.c_void_p] * 5),
+    ("az_net_wino_boards", C.c_int, [C.c_void_p]),
+    ("az_wino_boards_layout", C.c_int, [C.c_void_p] * 6),
     ("az_wino16_pack", C.c_int, [P(C.c_float), C.c_int, C.c_int, P(C.c_uint16), C.c_size_t, P(C.c_float)]),
     ("az_wino16_pack_rows", C.c_int, [P(C.c_float), C.c_int, P(C.c_uint16), C.c_size_t, P(C.c_float)]),
     ("az_net_load_mpk",C.c_int, [C.c_char_p, C.c_int, C.c_int, P(C.c_float), C.c_size_t]),

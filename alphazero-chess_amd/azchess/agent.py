@@ -167,6 +167,12 @@ class AlphaZero:
         return L.check(L.lib.az_net_wino_v_rows(self._h))
 
     @property
+    def wino_boards(self):
+        """Batch rows per workgroup of the split-f16 tower: 2 where the shared-row form runs two boards on one
+        weight stream (AZ_WINO_BOARDS=2), else 1; 0 when another kernel evaluates this net."""
+        return L.check(L.lib.az_net_wino_boards(self._h))
+
+    @property
     def winograd(self):
         return "Winograd" in self.tower_kernel
 
@@ -195,6 +201,15 @@ def wino_vrows_layout():
     t = dict(write=np.empty((16, 64, 4), np.int32), read=np.empty((2, 4, 4, 64), np.int32),
              act=np.empty((16, 64, 4), np.int32), item=np.empty((2, 8, 4), np.int32), dims=np.empty(4, np.int32))
     L.check(L.lib.az_wino_vrows_layout(*(t[k].ctypes.data_as(C.c_void_p) for k in ("write", "read", "act", "item", "dims"))))
+    return t
+
+
+def wino_boards_layout():
+    """az_wino_boards_layout: the two-board tower's item schedule, global activation offsets, epilogue
+    addresses and LDS regions (include/az.h), tabulated from the kernel's own constants; needs no device."""
+    t = dict(item=np.empty((8, 8, 2), np.int32), act=np.empty((2, 2), np.int32), out=np.empty((8, 64, 2, 4), np.int32),
+             vbuf=np.empty((2, 2), np.int32), zero=np.empty(64, np.int32), dims=np.empty(8, np.int32))
+    L.check(L.lib.az_wino_boards_layout(*(t[k].ctypes.data_as(C.c_void_p) for k in ("item", "act", "out", "vbuf", "zero", "dims"))))
     return t
 
 

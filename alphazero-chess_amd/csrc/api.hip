@@ -302,6 +302,13 @@ int az_net_wino_v_rows(az_net* net) {
     return n->fused && tower_supported(n) && wino_split16(n) && n->wino_rows && n->wino_vrows ? 1 : 0;
 }
 
+int az_net_wino_boards(az_net* net) {
+    if (!net) return fail("null argument");
+    const NetDev* n = net->dev;
+    if (!(n->fused && tower_supported(n) && wino_split16(n))) return 0;
+    return n->wino_rows && n->wino_vrows ? n->wino_boards : 1;
+}
+
 int az_wino16_pack(const float* folded, int filters, int streamed, uint16_t* out, size_t cap, float* unscale) {
     return wino16_pack(folded, filters, streamed, out, cap, unscale);
 }

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -30,6 +32,10 @@ static_assert(sizeof(azc::Pos) == sizeof(az_pos), "Pos == az_pos");
 // of a chunk, 1 all eight waves inside the steps (A/B: DESIGN.md 5.4)
 #ifndef AZ_WINO_VROWS_SCHED
 #define AZ_WINO_VROWS_SCHED 0
+#endif
+// boards per workgroup of the row-direct shared-row tower (wino.h wino_core_b2; C3 A/B: DESIGN.md 5.4)
+#ifndef AZ_WINO_BOARDS_DEFAULT
+#define AZ_WINO_BOARDS_DEFAULT 2
 #endif
 // weight ring steps of the row-direct form (wino.h WinoRing; C3 A/B of 2, 3, 4: DESIGN.md 5.4)
 #ifndef AZ_WINO_ROWS_PF
@@ -66,6 +72,11 @@ static inline bool wino16_rows(bool derive, bool rows, int filters) { return win
 // patch rows of every tile (32 KB: rows 2, 3 of a tile are rows 0, 1 of the tile below); the same bits
 // reach the same products.  Applies only where wino16_rows holds
 static inline bool wino16_vrows(bool rows_form, bool vrows) { return rows_form && vrows; }
+// AZ_WINO_BOARDS (1 or 2, default AZ_WINO_BOARDS_DEFAULT): in the shared-row form, 2 evaluates two batch
+// rows per workgroup on one weight stream, the residual convs' activations in global memory
+// (tower.hip tower32w2_kernel); the persistent per-game kernel stays on one board.  Applies only where
+// wino16_vrows holds
+static inline int wino16_boards(bool vrows_form, int boards) { return vrows_form && boards == 2 ? 2 : 1; }
 
 void set_error(const std::string& msg);
 int fail(const std::string& msg);
@@ -200,6 +211,14 @@ struct NetDev {
     bool wino_rows = false;         // wino16_w holds the row-direct stream (winograd_split16_rows)
     bool wino_vrows_env = AZ_WINO_VROWS_DEFAULT != 0;   // env AZ_WINO_VROWS=0/1 (wino16_vrows)
     bool wino_vrows = false;        // the row-direct kernel keeps V in the shared-row layout
+    int wino_boards_env = AZ_WINO_BOARDS_DEFAULT;       // env AZ_WINO_BOARDS=1/2 (wino16_boards)
+    int wino_boards = 1;            // batch rows per workgroup of tower_forward's kernel
+    // global ACT of the two-board tower (wino.h WINO_B2_WG bytes per workgroup): one allocation per stream
+    // that launches it (an arena and a search may run one net on two streams), grown on demand under
+    // b2_mu, freed with the net
+    struct B2Act { void* p = nullptr; int wgs = 0; };
+    std::map<hipStream_t, B2Act> b2_act;
+    std::mutex b2_mu;
     float* head = nullptr;          // folded head weights (f32)
     void* head_frag = nullptr;      // 1x1 F->40 head conv as bf16 hi/lo MFMA A-fragments (fused tower)
     void* in_pk32 = nullptr;        // f32 Winograd nets: the input conv's weights with channels 16-18 of 4 taps packed per k-step (tower32w)

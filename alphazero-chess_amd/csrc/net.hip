@@ -621,6 +621,7 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
     if (const char* e = getenv("AZ_WINO_DERIVE")) net->wino_derive = atoi(e) != 0;
     if (const char* e = getenv("AZ_WINO_ROWS")) net->wino_rows_env = atoi(e) != 0;
     if (const char* e = getenv("AZ_WINO_VROWS")) net->wino_vrows_env = atoi(e) != 0;
+    if (const char* e = getenv("AZ_WINO_BOARDS")) net->wino_boards_env = atoi(e);
     AZ_HIP(hipStreamCreateWithFlags(&net->stream, hipStreamNonBlocking));
     const float* p = wts;
     std::vector<uint8_t> w8h, w8sh;      // fp8: the residual convs' fragments, scale bytes and biases, uploaded below
@@ -678,6 +679,7 @@ int net_create(const az_net_desc* d, const float* wts, size_t n, int device, Net
             net->wino_streamed = wino16_streamed(net->wino_derive, F);
             net->wino_rows = wino16_rows(net->wino_derive, net->wino_rows_env, F);
             net->wino_vrows = wino16_vrows(net->wino_rows, net->wino_vrows_env);
+            net->wino_boards = wino16_boards(net->wino_vrows, net->wino_boards_env);
             auto u = net->wino_rows ? winograd_split16_rows(wf.data(), F, &us)
                                     : winograd_split16(wf.data(), F, net->wino_streamed, &us);
             void* du = nullptr;
@@ -797,6 +799,7 @@ void net_destroy(NetDev* n) {
     (void)hipFree(n->in_pk32);
     (void)hipFree(n->w8); (void)hipFree(n->w8s); (void)hipFree(n->b8);
     (void)hipFree(n->x); (void)hipFree(n->h); (void)hipFree(n->planes);
+    for (auto& kv : n->b2_act) (void)hipFree(kv.second.p);
     (void)hipFree(n->d_in); (void)hipFree(n->d_pol); (void)hipFree(n->d_val);
     net_update_free(n);
     if (n->stream) (void)hipStreamDestroy(n->stream);

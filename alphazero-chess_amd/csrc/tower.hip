@@ -628,6 +628,202 @@ tower32w_kernel(const float* __restrict__ planes, TowerArgs ta, const int* __res
     tower32w_board<F, SEARCH, H16, SP, ROWS, VROWS>(planes, ta, blockIdx.x, pol_out, val_out, so, threadIdx.x);
 }
 
+// ---- two boards per workgroup (AZ_WINO_BOARDS = 2, wino.h wino_core_b2): the 256-filter row-direct
+// shared-row tower with the residual convs' activations in global memory and both boards' MFMAs fed from
+// one weight stream.
+typedef unsigned int u32v4 __attribute__((__vector_size__(16)));
+// LDS of the two-board kernel, uint4 slots: V, then AUX (the larger of planes staging and heads scratch, in
+// 256-byte units), the input conv's zero row and the flag
+constexpr int WINO_B2_HS = (HeadsScratch<1, 512, heads_npart(512, true)>::FLOATS * 4 + 15) / 16;
+constexpr int WINO_B2_AUX = ((WINO_B2_HS > 64 * 10 ? WINO_B2_HS : 64 * 10) + 15) / 16 * 16;
+constexpr int WINO_B2_ZN = 16 + 256 / 4;
+constexpr int WINO_B2_LDS = (WINO_B2_VBYTES / 16 + WINO_B2_AUX + WINO_B2_ZN + 1) * 16;
+// where one board's ACT overlays V while the input conv and the heads run (bytes from the start of LDS)
+constexpr int WINO_B2_OVL = 0;
+static_assert(WINO_B2_OVL % 256 == 0 && WINO_B2_OVL + WINO_B2_ACT <= WINO_B2_VBYTES, "the ACT overlay lies inside V");
+// every vector memory operation of this wave has completed: before a workgroup hand-off (flag or barrier)
+// of global ACT stores, on top of the workgroup-scope fences that order them
+__device__ __forceinline__ void b2_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// one residual conv of both boards, global ACT -> global ACT: conv 1 of a block (RESID false) reads X and
+// writes H; conv 2 reads H, adds the residual from X -- read by the wave that owns those outputs, after the
+// accumulators are dead and before the same wave overwrites the same elements -- and writes X.
+template <bool RESID>
+__device__ __forceinline__ void conv_wino_b2(char* __restrict__ ldsv, const __amdgpu_buffer_rsrc_t rW,
+                                             const __amdgpu_buffer_rsrc_t rN, const __amdgpu_buffer_rsrc_t rA,
+                                             const float* __restrict__ bias, float unscale,
+                                             f32x4 (&wr)[WINO_B2_PF][2][2], int w, int lane, bool pre_in, bool pre_out,
+                                             int* flag, int seq, unsigned long long* tr = nullptr) {
+    constexpr int HIN = RESID ? 1 : 0, HOUT = 1 - HIN;
+    f32x4 acc[2][8][2];
+    wino_stamp(tr, 0);
+    wino_core_b2(ldsv, rW, rN, rA, HIN, wr, w, lane, pre_in, acc, tr);
+    wino_stamp(tr, 10);
+    const int ln = vgpr_index(lane);   // laundered: the epilogue's addresses are not kept through the chunk loop
+    const int co0 = w * 32 + (ln >> 4) * 4;
+    auto out_addr = [&](int n, int a, int b) { return wino_b2_out(w, ln, n, 2 * a + b); };
+    // one (board, output fragment) k = 2 nb + n at a time, its residual requested two fragments ahead (at most
+    // 32 VGPRs of residual and 16 of outputs beside the accumulators still to be transformed)
+    f32x4 xres[2][4];
+    auto xload = [&](int k) {
+        if constexpr (RESID) {
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                xres[k & 1][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                               rA, wino_b2_act(k >> 1, 0) + out_addr(k & 1, q >> 1, q & 1), 0, 0));
+        }
+    };
+    xload(0);
+    xload(1);
+    (void)xres;
+#pragma unroll
+    for (int nb = 0; nb < 2; nb++)
+#pragma unroll
+        for (int n = 0; n < 2; n++) {
+            f32x4 y[4];
+            wino_rows_out(acc[nb], bias, unscale, co0, n, y);
+            f32x4 o[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                o[q] = y[q];
+                if constexpr (RESID) o[q] += xres[n][q];
+            }
+            if (2 * nb + n + 2 < 4) xload(2 * nb + n + 2);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                f32x4 v = o[q];
+#pragma unroll
+                for (int r = 0; r < 4; r++) v[r] = relu_nan<true>(v[r]);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32v4, v), rA,
+                                                       wino_b2_act(nb, HOUT) + out_addr(n, q >> 1, q & 1), 0, 0);
+            }
+        }
+    wino_stamp(tr, 11);
+    b2_stores_done();
+    // the next conv's chunk 0 is this conv's output channels 0-31 of either board, all written by wave 0:
+    // as in conv_wino, waves 0-3 transform it into the V buffers 0 while waves 4-7 finish; wave 0's global
+    // stores are published to waves 1-3 through the LDS flag
+    if (pre_out && w < 4) {
+        if (w == 0) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        else
+            while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seq)
+                __builtin_amdgcn_s_sleep(1);
+        wino_b2_items<4>(ldsv, rA, HOUT, 0, 0, w, lane);
+    }
+    __syncthreads();
+}
+
+// batch rows row0 and (nbv = 2) row0 + 1 through the tower.  LDS: the four V buffers (80 KB), overlaid by
+// one board's ACT [64 squares][66 slots] while the input conv and the heads run, one board after the
+// other; AUX (planes staging, heads scratch); the zero row of the input conv and the hand-off flag.
+// act: this workgroup's WINO_B2_WG bytes of global ACT.  An absent second board runs on zero planes and
+// writes nothing out.
+template <bool SEARCH>
+__device__ __forceinline__ void tower32w_boards2(const float* __restrict__ planes, const TowerArgs& ta, int row0, int nbv,
+                                                 char* __restrict__ act, float* __restrict__ pol_out,
+                                                 float* __restrict__ val_out, const SearchOut& so, int tid) {
+    constexpr int F = 256, NT = 512, NN = 2, RSF = F / 4 + 2, RSI = 32 / 4 + 2, PF = WINO_B2_PF;
+    constexpr int VSZ = WINO_B2_VBYTES / 16, AUX = WINO_B2_AUX, ZN = WINO_B2_ZN;   // uint4 slots
+    static_assert(64 * RSF <= VSZ && 64 * RSF * 16 == WINO_B2_ACT, "one board's ACT overlays V");
+    static_assert(64 * RSI <= AUX, "input planes must fit in AUX");
+    static_assert((VSZ + AUX) * 16 % 256 == 0, "conv32_in_packed ORs the zero row's offset into the low byte");
+    static_assert(WINO_B2_LDS <= 163840, "LDS of a CU");
+    __shared__ __attribute__((aligned(16))) uint4 lds[VSZ + AUX + ZN + 1];
+    const int lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    char* ldsb = reinterpret_cast<char*>(lds);
+    char* actl = ldsb + WINO_B2_OVL;                     // the overlaid ACT
+    uint4* A = lds + VSZ;
+    const int zero_off = (VSZ + AUX) * 16;
+    int* flag = reinterpret_cast<int*>(lds + VSZ + AUX + ZN);
+    const __amdgpu_buffer_rsrc_t rA = t32_rsrc(reinterpret_cast<const uint4*>(act), WINO_B2_WG);
+    unsigned long long* tr = nullptr;
+#ifdef AZ_TOWER_TRACE
+    tr = tt_slot(w);
+#endif
+    wino_stamp(tr, 0);
+    for (int c = tid; c < ZN + 1; c += NT) lds[VSZ + AUX + c] = make_uint4(0, 0, 0, 0);   // zero row + the flag
+#pragma unroll 1
+    for (int nb = 0; nb < 2; nb++) {
+        stage_planes_f32<1, RSI, NT>(A, planes, so, row0 + nb, nb < nbv ? 1 : 0, tid);
+        __syncthreads();
+        if (nb == 0) wino_stamp(tr, 1);
+        {   // input conv 19 -> F into the overlaid ACT, as tower32w_board
+            f32x4 wr[T32_PF][NN];
+            const __amdgpu_buffer_rsrc_t r0 = t32_rsrc(ta.w0pk, ta.w0pk_bytes);
+            const int voff = ((w * NN) * 64 + lane) * 16;
+#pragma unroll
+            for (int i = 0; i < T32_PF; i++)
+#pragma unroll
+                for (int n = 0; n < NN; n++)
+                    wr[i][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                             r0, voff + n * 1024 + i * (F / 16) * 1024, 0, 0));
+            conv32_in_packed<F, RSI, RSF, NN>(ldsb, actl, VSZ * 16, zero_off, r0, ta.b[0], wr, w, lane);
+        }
+        // ACT -> the board's X: the 64 channel slots of every square
+        for (int i = tid; i < 64 * 64; i += NT) {
+            const int o = ((i >> 6) * RSF + (i & 63)) * 16;
+            __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32v4*>(actl + o), rA, wino_b2_act(nb, 0) + o, 0, 0);
+        }
+        b2_stores_done();
+        __syncthreads();
+    }
+    // rows 0 and 9 of the four V buffers' planes: 64 runs of 256 B, never written by an item
+    static_assert(NT == 32 * 16, "two uint4 of the zero rows per thread");
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+        *reinterpret_cast<uint4*>(ldsb + wino_vr_zero((tid >> 4) + 32 * k) + (tid & 15) * 16) = make_uint4(0, 0, 0, 0);
+    wino_stamp(tr, 2);
+    f32x4 wring[PF][2][NN];
+    if (ta.blocks > 0) {
+        const __amdgpu_buffer_rsrc_t r = t32_rsrc(ta.ww[0], ta.wwbytes[0]);
+        const int voff = wino16_voff<F>(w, lane);
+#pragma unroll
+        for (int i = 0; i < PF; i++)
+#pragma unroll
+            for (int pl = 0; pl < 2; pl++)
+#pragma unroll
+                for (int n = 0; n < NN; n++)
+                    wring[i][pl][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                                    r, voff + (2 * n + pl) * 1024 + i * (F / 16) * 2048, 0, 0));
+    }
+    for (int b = 0; b < ta.blocks; b++) {
+        const unsigned wb3 = b + 1 < ta.blocks ? ta.wwbytes[2 * b + 2] : 0u;   // after the last conv: nothing (reads 0)
+        const __amdgpu_buffer_rsrc_t r1 = t32_rsrc(ta.ww[2 * b], ta.wwbytes[2 * b]);
+        const __amdgpu_buffer_rsrc_t r2 = t32_rsrc(ta.ww[2 * b + 1], ta.wwbytes[2 * b + 1]);
+        const __amdgpu_buffer_rsrc_t r3 = t32_rsrc(b + 1 < ta.blocks ? ta.ww[2 * b + 2] : ta.ww[2 * b + 1], wb3);
+        conv_wino_b2<false>(ldsb, r1, r2, rA, ta.b[1 + 2 * b], ta.wus[2 * b], wring, w, lane, b > 0, true, flag, 2 * b + 1,
+                            tr ? tr + 3 + 64 * b : nullptr);
+        conv_wino_b2<true>(ldsb, r2, r3, rA, ta.b[2 + 2 * b], ta.wus[2 * b + 1], wring, w, lane, true, b + 1 < ta.blocks, flag,
+                           2 * b + 2, tr ? tr + 35 + 64 * b : nullptr);
+    }
+    // heads: the board's X back into the overlaid ACT, one board after the other.  The thread index is made
+    // again from the wave's and the lane's (kept from the kernel's entry through the convs it was spilled)
+    tid = w * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+#pragma unroll 1
+    for (int nb = 0; nb < nbv; nb++) {
+        for (int i = tid; i < 64 * 64; i += NT) {
+            const int o = ((i >> 6) * RSF + (i & 63)) * 16;
+            *reinterpret_cast<u32v4*>(actl + o) = __builtin_amdgcn_raw_buffer_load_b128(rA, wino_b2_act(nb, 0) + o, 0, 0);
+        }
+        __syncthreads();
+        heads_group<F, RSF, 1, NT, SEARCH, true, true>(actl, reinterpret_cast<float*>(A), 0, 1, row0 + nb, tid, ta.head_frag32,
+                                                       ta.head, pol_out, val_out, so, tr);
+    }
+    wino_stamp(tr, 3 + 64 * 20);
+}
+
+template <bool SEARCH>
+__global__ void __launch_bounds__(512)
+tower32w2_kernel(const float* __restrict__ planes, TowerArgs ta, const int* __restrict__ count_ptr, int rows,
+                 char* __restrict__ act, float* __restrict__ pol_out, float* __restrict__ val_out, SearchOut so) {
+    const int count = count_ptr ? min(load_fresh(count_ptr), rows) : rows;
+    const int row0 = 2 * (int)blockIdx.x;
+    if (row0 >= count) return;
+    tower32w_boards2<SEARCH>(planes, ta, row0, min(2, count - row0), act + (size_t)blockIdx.x * WINO_B2_WG, pol_out, val_out,
+                             so, threadIdx.x);
+}
+
 // k_sims32w: simulation steps [step0, step1) of one game per workgroup, with no grid-wide step
 // boundary.  A game's simulations only touch its own tree (tree.rs:180-207 runs them one after
 // the other per game), so the workgroup of game g loops: wave 0 backs up the previous
@@ -771,6 +967,25 @@ int sims_persistent(const NetDev* n, const Engine& E, const SearchOut& so, int s
     return fail("persistent simulation kernel: unsupported filters");
 }
 
+// the global ACT of stream st's two-board launches, at least `wgs` workgroups of WINO_B2_WG bytes.  Growing
+// waits for the stream's earlier launches (they use the old allocation) before freeing it.  The lock covers the
+// map and the allocation, not the launch that follows: a stream is used by one host thread at a time, as
+// everywhere in this library.  An entry stays until net_destroy, also after its stream is gone
+static char* b2_act_for(NetDev* n, hipStream_t st, int wgs) {
+    std::lock_guard<std::mutex> lock(n->b2_mu);
+    NetDev::B2Act& a = n->b2_act[st];
+    if (wgs > a.wgs) {
+        if (a.p) {
+            if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
+            (void)hipFree(a.p);
+        }
+        a = NetDev::B2Act();
+        if (hipMalloc(&a.p, (size_t)wgs * WINO_B2_WG) != hipSuccess) { a.p = nullptr; return nullptr; }
+        a.wgs = wgs;
+    }
+    return static_cast<char*>(a.p);
+}
+
 int tower_forward(NetDev* n, const void* planes, const int* count, int rows, float* pol, float* val,
                   const SearchOut* so, hipStream_t st) {
     if (rows <= 0) return 0;
@@ -808,6 +1023,15 @@ int tower_forward(NetDev* n, const void* planes, const int* count, int rows, flo
             return hipGetLastError() == hipSuccess ? 0 : fail("f32 Winograd tower launch failed");             \
         }
         if (wino_split16(n)) {
+            if (n->filters == 256 && n->wino_streamed == 12 && n->wino_rows && n->wino_vrows && n->wino_boards == 2) {
+                // two batch rows per workgroup, their residual activations in the stream's global ACT
+                const int grid = (rows + 1) / 2;
+                char* act = b2_act_for(n, st, grid);
+                if (!act) return fail("two-board tower: global activations allocation failed");
+                if (so) tower32w2_kernel<true><<<grid, 512, 0, st>>>((const float*)planes, ta, count, rows, act, pol, val, s);
+                else tower32w2_kernel<false><<<grid, 512, 0, st>>>((const float*)planes, ta, count, rows, act, pol, val, s);
+                return hipGetLastError() == hipSuccess ? 0 : fail("f32 Winograd tower launch failed");
+            }
             if (n->wino_streamed == 12 && n->wino_rows && n->wino_vrows) { AZ_TOWER32W(256, true, 12, true, true) }
             if (n->wino_streamed == 12 && n->wino_rows) { AZ_TOWER32W(256, true, 12, true, false) }
             if (n->wino_streamed == 12) { AZ_TOWER32W(256, true, 12, false, false) }
@@ -851,6 +1075,30 @@ extern "C" int az_wino_vrows_layout(int* write, int* read, int* act, int* item, 
                 item[(sched * 8 + wave) * 4 + it] = wave < nw && it < WINO_VR_ITEMS / nw ? wino_vr_item(wave, it, nw) : -1;
             }
     dims[0] = WINO_VR_PLANE; dims[1] = WINO_VR_BYTES; dims[2] = WINO_VR_R16; dims[3] = 4;
+    return 0;
+}
+
+// the two-board tower's layout (wino.h wino_b2_*, the LDS regions of tower32w_boards2), tabulated on the host
+extern "C" int az_wino_boards_layout(int* item, int* act, int* out, int* vbuf, int* zero, int* dims) {
+    using namespace azi;
+    if (!item || !act || !out || !vbuf || !zero || !dims) return fail("null argument");
+    for (int w = 0; w < 8; w++)
+        for (int k = 0; k < 8; k++) {
+            item[(w * 8 + k) * 2] = k < wino_b2_item_count(w) ? wino_b2_item_board(w, k) : -1;
+            item[(w * 8 + k) * 2 + 1] = k < wino_b2_item_count(w) ? wino_b2_item_q(w, k) : -1;
+        }
+    for (int nb = 0; nb < 2; nb++)
+        for (int b = 0; b < 2; b++) {
+            act[nb * 2 + b] = wino_b2_act(nb, b);
+            vbuf[nb * 2 + b] = wino_b2_v(nb, b);
+        }
+    for (int w = 0; w < 8; w++)
+        for (int lane = 0; lane < 64; lane++)
+            for (int n = 0; n < 2; n++)
+                for (int q = 0; q < 4; q++) out[((w * 64 + lane) * 2 + n) * 4 + q] = wino_b2_out(w, lane, n, q);
+    for (int k = 0; k < 64; k++) zero[k] = wino_vr_zero(k);
+    dims[0] = WINO_B2_ACT; dims[1] = WINO_B2_WG; dims[2] = WINO_VR_BYTES; dims[3] = WINO_B2_OVL; dims[4] = WINO_B2_ACT;
+    dims[5] = WINO_B2_VBYTES; dims[6] = WINO_B2_AUX * 16; dims[7] = WINO_B2_LDS;
     return 0;
 }
 

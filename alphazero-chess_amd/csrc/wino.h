@@ -1031,4 +1031,212 @@ __device__ __forceinline__ void wino_core_h16(char* __restrict__ ldsb, int vbase
     }
 }
 
+// ====================================================================== two boards per workgroup
+// wino_core_b2 (AZ_WINO_BOARDS = 2): the row-direct shared-row form (wino_core_h16<256, 12, true, true>) on two
+// boards at once.  Every A fragment the ring delivers feeds both boards' B fragments, so a CU pulls the
+// conv's weights from L2 once per pair of boards instead of once per board; per board the products, their
+// order and K are the one-board kernel's, so each board's result is bit-equal to it.
+//   ACT      lives in global memory (L2-resident): per workgroup and board two buffers X (block input /
+//            output) and H (conv 1's output) in ACT's [64 squares][66 slots] f32 layout (WINO_B2_*), read
+//            and written through a buffer descriptor of the workgroup's WINO_B2_WG bytes; the wino_vr_a*
+//            address functions apply unchanged from the buffer's offset.  LDS holds only V;
+//   V        two buffers per board, board nb's buffer `buf` at (2 nb + buf) WINO_VR_BYTES: 80 KB;
+//   step     12 MFMAs per board, board 0's then board 1's; each board's four B fragments (planes n0 and
+//            n0 + 1, hi and lo: 16 VGPRs) are held for the step at hand, and what the next step needs of
+//            them is read as soon as the board's MFMAs have issued, i.e. one board ahead;
+//   ring     WINO_B2_PF steps, each slot refilled after the step's MFMAs have read it (no copy);
+//   items    the next chunk's transform inside the steps, one item at a time: item k's four global reads at
+//            the top of step k, its transform and V writes at the top of step k + 1 -- a step of MFMAs covers
+//            the L2 round trip, 4 VGPRs in flight.  The matrix pipe serves the first wave of each SIMD pair
+//            first: with the 32 items spread evenly (4 per wave) waves 0-3 ran 3,400 cycles per chunk ahead of
+//            their partners and waited 3,800 at every chunk barrier, while a wave alone on its SIMD runs at
+//            the loads' latency, not at the pipe's rate; with all 32 on waves 0-3 (8 each) those arrived
+//            2,600 cycles late.  They take WINO_B2_XE = 6 each and waves 4-7 two (profiles/boards2_trace.txt).
+// The accumulators are returned to the caller (tower.hip conv_wino_b2), whose epilogue reads the residual
+// from global ACT once they are dead.
+constexpr int WINO_B2_ACT = 64 * WINO_VR_R16;          // one ACT buffer, 67,584 B
+constexpr int WINO_B2_BOARD = 2 * WINO_B2_ACT;         // X, then H
+constexpr int WINO_B2_WG = 2 * WINO_B2_BOARD;          // 270,336 B of global ACT per workgroup
+constexpr int WINO_B2_VBYTES = 4 * WINO_VR_BYTES;      // the four V buffers
+#ifndef AZ_WINO_B2_PF
+#define AZ_WINO_B2_PF 3
+#endif
+constexpr int WINO_B2_PF = AZ_WINO_B2_PF;
+static_assert(12 % WINO_B2_PF == 0 && WINO_B2_PF >= 2, "the ring's slots must be compile-time");
+// byte offset of board nb's buffer (0: X, 1: H) in the workgroup's global ACT, of its V buffer in LDS
+__host__ __device__ constexpr int wino_b2_act(int nb, int hbuf) { return nb * WINO_B2_BOARD + hbuf * WINO_B2_ACT; }
+__host__ __device__ constexpr int wino_b2_v(int nb, int buf) { return (2 * nb + buf) * WINO_VR_BYTES; }
+// the epilogue's access of wave w's lane (conv_wino's out_addr): output fragment n, square q of the lane's tile
+// (2 ty + q / 2, 2 tx + q % 2), channels 32 w + 16 n + 4 (lane >> 4) .. + 3, bytes within an ACT buffer
+__host__ __device__ constexpr int wino_b2_out(int w, int lane, int n, int q) {
+    const int l16 = lane & 15, ty = l16 >> 2, tx = l16 & 3;
+    return ((2 * ty + (q >> 1)) * 8 + 2 * tx + (q & 1)) * WINO_VR_R16 + (w * 32 + (lane >> 4) * 4 + n * 16) * 4;
+}
+// the in-step schedule: a chunk's 32 items g = 16 board + wave-item; each of waves 0-3 takes WINO_B2_XE of
+// them (g = w + 4 k), each of waves 4-7 the rest (WINO_B2_XL = 8 - WINO_B2_XE each)
+#ifndef AZ_WINO_B2_XE
+#define AZ_WINO_B2_XE 6
+#endif
+constexpr int WINO_B2_XE = AZ_WINO_B2_XE, WINO_B2_XL = 8 - WINO_B2_XE;
+static_assert(WINO_B2_XE >= 4 && WINO_B2_XE <= 8, "waves 0-3 take at least their share, at most everything");
+__host__ __device__ constexpr int wino_b2_item_count(int w) { return w < 4 ? WINO_B2_XE : WINO_B2_XL; }
+__host__ __device__ constexpr int wino_b2_item_g(int w, int k) { return w < 4 ? w + 4 * k : 4 * WINO_B2_XE + (w - 4) + 4 * k; }
+__host__ __device__ constexpr int wino_b2_item_board(int w, int k) { return wino_b2_item_g(w, k) >> 4; }
+__host__ __device__ constexpr int wino_b2_item_q(int w, int k) { return wino_b2_item_g(w, k) & 15; }
+
+// wave-item q of chunk c from the global ACT buffer at byte offset aoff: the four reads of WinoXf::vr_load
+__device__ __forceinline__ void wino_b2_load(const __amdgpu_buffer_rsrc_t rA, int aoff, int c, int q, float (&e)[4], int ln) {
+    const int tl = ln >> 4;
+    const int p = wino_vr_alane(ln) + wino_vr_auni(q) + c * 128 + aoff;
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        e[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rA, p + wino_vr_acol(tl, j), 0, 0));
+}
+// chunk c of both boards into their V buffers `buf` by the first NW waves, every read issued before the
+// first transform (for use where the accumulators are dead: 4 x 2 x 16 / NW VGPRs of patch values)
+template <int NW>
+__device__ __forceinline__ void wino_b2_items(char* __restrict__ ldsv, const __amdgpu_buffer_rsrc_t rA, int hbuf, int c,
+                                              int buf, int w, int lane) {
+    constexpr int NI = WINO_VR_ITEMS / NW;
+    const int ln = vgpr_index(lane);
+    float e[2][NI][4];
+#pragma unroll
+    for (int nb = 0; nb < 2; nb++)
+#pragma unroll
+        for (int i = 0; i < NI; i++) wino_b2_load(rA, wino_b2_act(nb, hbuf), c, wino_vr_item(w, i, NW), e[nb][i], ln);
+#pragma unroll
+    for (int nb = 0; nb < 2; nb++) {
+        const WinoXf<256> xf(ldsv, wino_b2_v(nb, 0), w, lane);
+#pragma unroll
+        for (int i = 0; i < NI; i++) xf.vr_store(buf, wino_vr_item(w, i, NW), e[nb][i], ln);
+    }
+}
+
+// the output transform of the row-direct form for one board's output fragment n: wino_core_h16's, operation
+// for operation
+__device__ __forceinline__ void wino_rows_out(const f32x4 (&acc)[8][2], const float* __restrict__ bias, float unscale,
+                                              int co0, int n, f32x4 (&y)[4]) {
+    const f32x2 us = f32x2{unscale, unscale};
+    {
+        const f32x4 bb = *reinterpret_cast<const f32x4*>(bias + co0 + n * 16);
+#pragma unroll
+        for (int p = 0; p < 2; p++) {
+            f32x2 s0[4], s1[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                s0[j] = p ? f32x2{acc[j][n][2], acc[j][n][3]} : f32x2{acc[j][n][0], acc[j][n][1]};
+                s1[j] = p ? f32x2{acc[4 + j][n][2], acc[4 + j][n][3]} : f32x2{acc[4 + j][n][0], acc[4 + j][n][1]};
+            }
+            const f32x2 br = p ? f32x2{bb[2], bb[3]} : f32x2{bb[0], bb[1]};
+            const f32x2 q0 = pkc_fma(pk_add(pk_add(s0[0], s0[1]), s0[2]), us, br);
+            const f32x2 q1 = pkc_fma(pk_sub(pk_sub(s0[1], s0[2]), s0[3]), us, br);
+            const f32x2 q2 = pkc_fma(pk_add(pk_add(s1[0], s1[1]), s1[2]), us, br);
+            const f32x2 q3 = pkc_fma(pk_sub(pk_sub(s1[1], s1[2]), s1[3]), us, br);
+            y[0][2 * p] = q0.x; y[0][2 * p + 1] = q0.y;
+            y[1][2 * p] = q1.x; y[1][2 * p + 1] = q1.y;
+            y[2][2 * p] = q2.x; y[2][2 * p + 1] = q2.y;
+            y[3][2 * p] = q3.x; y[3][2 * p + 1] = q3.y;
+        }
+    }
+}
+
+// ldsv: the four V buffers; rA: the workgroup's global ACT, hin: the conv's input buffer (0: X, 1: H);
+// pre: chunk 0 is in V already (conv_wino_b2's hand-off); acc[nb]: board nb's eight row sums per fragment
+__device__ __forceinline__ void wino_core_b2(char* __restrict__ ldsv, const __amdgpu_buffer_rsrc_t rW,
+                                             const __amdgpu_buffer_rsrc_t rN, const __amdgpu_buffer_rsrc_t rA, int hin,
+                                             f32x4 (&wr)[WINO_B2_PF][2][2], int w, int lane, bool pre,
+                                             f32x4 (&acc)[2][8][2], unsigned long long* tr = nullptr) {
+    constexpr int F = 256, CF = F / 16, NN = 2, PF = WINO_B2_PF, NCHUNK = 8, SPX = 12, STEPB = CF * 2 * 1024;
+    const int vr0 = wino_vr_rlane(lane, 0), vr1 = wino_vr_rlane(lane, 1);
+#pragma unroll
+    for (int nb = 0; nb < 2; nb++)
+#pragma unroll
+        for (int x = 0; x < 8; x++)
+#pragma unroll
+            for (int n = 0; n < NN; n++) {
+                f32x2 z0, z1;
+                asm volatile("v_mov_b64 %0, 0" : "=v"(z0));
+                asm volatile("v_mov_b64 %0, 0" : "=v"(z1));
+                acc[nb][x][n] = f32x4{z0.x, z0.y, z1.x, z1.y};
+            }
+    const int voff = wino16_voff<F>(w, lane);
+    if (!pre) {   // chunk 0 not transformed by the caller
+        wino_b2_items<8>(ldsv, rA, hin, 0, 0, w, lane);
+        __syncthreads();
+    }
+    wino_stamp(tr, 1);
+#pragma unroll 1
+    for (int c = 0; c < NCHUNK; c++) {
+        const bool more = c + 1 < NCHUNK;
+        // planes numbered n = 4 b + i in the order the steps meet them (wino_core_h16), plane n in slot n % 2:
+        // step (b, k) multiplies planes n0 = 4 b + k and n0 + 1; the next step of the column keeps n0 + 1 and
+        // reads n0 + 2 into the slot n0 leaves, a new column reads both
+        f16x8 bw[2][2][2];                                           // [board][slot][hi, lo]
+        float en[4];                                                 // the item in flight
+        auto bread = [&](int nb, int st) {
+            const char* vb = ldsv + wino_b2_v(nb, c & 1);
+#pragma unroll
+            for (int s = st % 3 == 0 ? 0 : 1; s < 2; s++) {
+                const int n = 4 * (st / 3) + st % 3 + s;             // patch row n % 4 of point n / 4
+                const int vl = (n % 4) >> 1 ? vr1 : vr0;
+                const char* p = vb + wino_vr_rimm(n % 4, n / 4);
+                bw[nb][n % 2][0] = *reinterpret_cast<const f16x8*>(p + vl);
+                bw[nb][n % 2][1] = *reinterpret_cast<const f16x8*>(p + wino_vr_lo(vl));
+            }
+        };
+        bread(0, 0);
+        bread(1, 0);
+#pragma unroll
+        for (int st = 0; st < SPX; st++) {
+            const int b = st / 3;
+            // the next chunk's items (waves 0-3): item st - 1 into V[(c + 1) & 1], free since the previous chunk's
+            // barrier, then item st's reads -- issued before the step's refill, so that the wait a step later
+            // leaves the ring's loads in flight
+            if (more) {
+                if (st >= 1 && st <= wino_b2_item_count(w)) {
+                    const WinoXf<F> xf(ldsv, wino_b2_v(wino_b2_item_board(w, st - 1), 0), w, lane);
+                    xf.vr_store((c + 1) & 1, wino_b2_item_q(w, st - 1), en, vgpr_index(lane));
+                }
+                if (st < wino_b2_item_count(w))
+                    wino_b2_load(rA, wino_b2_act(wino_b2_item_board(w, st), hin), c + 1, wino_b2_item_q(w, st), en, vgpr_index(lane));
+            }
+#pragma unroll
+            for (int nb = 0; nb < 2; nb++) {
+                __builtin_amdgcn_sched_barrier(0);
+                // W[k][b] against D[k][b] into s0[b] and against D[k + 1][b] into s1[b]: hi hi, hi lo, lo hi of
+                // each, four chains interleaved (wino_core_h16's order)
+#pragma unroll
+                for (int term = 0; term < 3; term++)
+#pragma unroll
+                    for (int pt = 0; pt < 2; pt++)
+#pragma unroll
+                        for (int n = 0; n < NN; n++) {
+                            const f16x8 av = __builtin_bit_cast(f16x8, wr[st % PF][term == 2 ? 1 : 0][n]);
+                            const f16x8 bv = bw[nb][(4 * b + st % 3 + pt) % 2][term == 1 ? 1 : 0];
+                            acc[nb][4 * pt + b][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc[nb][4 * pt + b][n], 0, 0, 0);
+                        }
+                __builtin_amdgcn_sched_barrier(0);
+                if (nb == 1) {
+                    // ring step st + PF into the slot just read; past this conv's last step the next conv's first
+                    const bool nxt = st + PF >= SPX && !more;
+                    const int tn = c * SPX + st + PF;
+                    const int to = nxt ? tn - NCHUNK * SPX : tn;
+#pragma unroll
+                    for (int pl = 0; pl < 2; pl++)
+#pragma unroll
+                        for (int n = 0; n < NN; n++)
+                            wr[st % PF][pl][n] = __builtin_bit_cast(
+                                f32x4, __builtin_amdgcn_raw_buffer_load_b128(nxt ? rN : rW, voff + (2 * n + pl) * 1024,
+                                                                             to * STEPB, 0));
+                }
+                if (st + 1 < SPX) bread(nb, st + 1);
+            }
+            if (st == 4) wino_stamp(tr, 20 + c);
+        }
+        wino_stamp(tr, 12 + c);
+        if (more) __syncthreads();   // (none after the last chunk: see wino_core)
+        wino_stamp(tr, 2 + c);
+    }
+}
+
 }  // namespace azi

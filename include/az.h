@@ -101,6 +101,20 @@ int az_net_wino_accumulators(az_net* net);
 /* 1 where the row-direct split-f16 tower keeps its transformed input with every row of the padded board
  * stored once (AZ_WINO_VROWS, only where az_net_wino_accumulators is 8), 0 otherwise */
 int az_net_wino_v_rows(az_net* net);
+/* batch rows per workgroup of the kernel that evaluates this net's batches: 2 where the shared-row tower
+ * runs two boards on one weight stream with its activations in global memory (AZ_WINO_BOARDS=2, only
+ * where az_net_wino_v_rows is 1), 1 for every other form of the split-f16 tower, 0 for a net that another
+ * kernel evaluates */
+int az_net_wino_boards(az_net* net);
+/* The two-board tower's layout, tabulated from the constants and address functions the kernel uses
+ * (wino.h wino_b2_*, wino_vr_*), byte offsets: item[wave][k] = {board, wave-item} of the wave's k-th
+ * transform item of a chunk, or -1 past the wave's last item (8 x 8 x 2); act[board][buffer] of the board's X (0) and H (1) within the
+ * workgroup's global activations (2 x 2); out[wave][lane][n][q] of the lane's epilogue access (output
+ * fragment n, square q of its tile) within a buffer (8 x 64 x 2 x 4, 16 bytes each); vbuf[board][buf] of
+ * the V buffers in LDS (2 x 2); zero[k] of the 64 runs of 256 B that are the off-board rows; dims =
+ * {buffer bytes, global bytes per workgroup, V buffer bytes, LDS ACT overlay offset, LDS ACT overlay
+ * bytes, AUX offset, AUX bytes, total LDS bytes}.  Needs no device. */
+int az_wino_boards_layout(int* item, int* act, int* out, int* vbuf, int* zero, int* dims);
 /* The shared-row V layout's address functions, tabulated from the formulas the kernel uses (wino.h
  * wino_vr_*), byte offsets: write[q][lane][b] of wave-item q (16 per chunk), point b within a chunk's V
  * buffer (16 x 64 x 4); read[plane][i][b][lane] of patch row i, point b in the hi and the lo plane
