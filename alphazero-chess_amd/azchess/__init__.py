@@ -9,8 +9,8 @@ from .agent import (AlphaZero, load_model, load_mpk, mx8_conv_probe, mx8_quantiz
 from .chess import (GameResult, GameState, IllegalMove, Position, get_best_move, index_to_move, minimax_scores,
                     move_to_index, play_move, to_tensor)
 from .memory import ReplayBuffer, TrainingSample
-from .training import (EpisodeStep, SelfPlay, Trainer, comm_unique_id, get_cyclical_lr, process_batch,
-                       run_all_episodes, run_episode, train)
+from .training import (EpisodeStep, SelfPlay, Trainer, agree_verdict, comm_unique_id, gate_seed, gate_verdict,
+                       get_cyclical_lr, process_batch, run_all_episodes, run_episode, train)
 from .tree import BatchedSearch, MCTree, make_cfg
 from .validation import Arena, EvaluationResult, Player, compute_elo_rankings, compute_elos, evaluate
 
@@ -18,4 +18,5 @@ __all__ = ["AlphaZero", "load_model", "load_mpk", "save_mpk", "num_params", "ran
            "index_to_move", "move_to_index", "play_move", "to_tensor", "EpisodeStep", "SelfPlay", "Trainer", "comm_unique_id",
            "get_cyclical_lr", "process_batch", "train", "ReplayBuffer", "TrainingSample",
            "run_all_episodes", "run_episode", "BatchedSearch", "MCTree", "make_cfg", "parameters", "EvaluationResult", "Player",
-           "compute_elo_rankings", "compute_elos", "evaluate", "Arena", "get_best_move", "minimax_scores", "mx8_quantize", "mx8_conv_probe"]
+           "compute_elo_rankings", "compute_elos", "evaluate", "Arena", "get_best_move", "minimax_scores", "mx8_quantize", "mx8_conv_probe",
+           "gate_seed", "gate_verdict", "agree_verdict"]

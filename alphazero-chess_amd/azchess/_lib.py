@@ -161,6 +161,12 @@ SIGNATURES = [
                                   P(C.c_float)]),
     ("az_trainer_get_params", C.c_int, [C.c_void_p, P(C.c_float), C.c_size_t]),
     ("az_trainer_get_grads", C.c_int, [C.c_void_p, P(C.c_float), C.c_size_t]),
+    ("az_trainer_set_params", C.c_int, [C.c_void_p, P(C.c_float), C.c_size_t]),
+    ("az_trainer_set_params_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("az_trainer_snapshot", C.c_int, [C.c_void_p]),
+    ("az_trainer_restore", C.c_int, [C.c_void_p]),
+    ("az_trainer_get_snapshot", C.c_int, [C.c_void_p, P(C.c_float), C.c_size_t]),
+    ("az_trainer_adamw_steps", C.c_int64, [C.c_void_p]),
     ("az_trainer_relu_output", C.c_int, [C.c_void_p, C.c_int, P(C.c_float), C.c_size_t]),
     ("az_trainer_timing", C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double), P(C.c_int64), C.c_int]),
     ("az_comm_unique_id", C.c_int, [C.c_void_p, C.c_int]),

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib as L
 from .chess import Position, to_tensor
 from .parameters import (BATCH_SIZE, EVALUATION_GAMES, MIN_REPLAY_SIZE, NUM_EPISODES, NUM_FILTERS, NUM_RES_BLOCKS,
-                         NUM_SIMULATIONS, NUM_TRAIN_STEPS, SEED)
+                         NUM_SIMULATIONS, NUM_TRAIN_STEPS, SEED, WIN_RATE_THRESHOLD)
 from .tree import BatchedSearch
 
 
@@ -227,6 +227,40 @@ class Trainer:
         L.check(L.lib.az_trainer_get_grads(self._h, L.fptr(out), self.n))
         return out
 
+    def set_params(self, weights):
+        """Replace the flat parameters (running statistics included) from a host array; the AdamW
+        moments, the step count, the last gradients and every setting stay (az_trainer_set_params).
+        Not a collective: at world > 1 every rank makes the same call."""
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        L.check(L.lib.az_trainer_set_params(self._h, L.fptr(w), w.size))
+
+    def set_params_device(self, weights, n=None, stream=None):
+        """set_params from `n` (default: all) f32 already in this GPU's memory (an address or an object
+        with data_ptr()), ordered after what `stream` holds (az_trainer_set_params_device)."""
+        from .memory import dev_ptr
+        L.check(L.lib.az_trainer_set_params_device(self._h, dev_ptr(weights), self.n if n is None else int(n),
+                                                   dev_ptr(stream)))
+
+    def snapshot(self):
+        """new_model = model.clone() (training.rs:132): keep a copy of the current parameters in HBM
+        (one per trainer; a later snapshot overwrites it)."""
+        L.check(L.lib.az_trainer_snapshot(self._h))
+
+    def restore(self):
+        """Parameters <- the snapshot (a rejected candidate, training.rs:231); the AdamW state is not
+        rolled back, as the reference's optimizer lives outside the loop."""
+        L.check(L.lib.az_trainer_restore(self._h))
+
+    def snapshot_params(self):
+        out = np.empty(self.n, np.float32)
+        L.check(L.lib.az_trainer_get_snapshot(self._h, L.fptr(out), self.n))
+        return out
+
+    @property
+    def adamw_steps(self):
+        """Optimizer steps applied so far (burn's AdaptiveMomentumWState::time)."""
+        return int(L.check(L.lib.az_trainer_adamw_steps(self._h)))
+
     def relu_masks(self, batch):
         """ReLU masks of the last forward in forward order (parity tests): tower layers as
         NCHW [B, F, 8, 8], heads [B, 40, 8, 8], value hidden [B, 64]."""
@@ -329,16 +363,36 @@ def elo_seed(seed, iteration):
     return (seed << 20) ^ (iteration << 8) ^ 0xE10
 
 
+def gate_seed(seed, iteration):
+    """Seed of an iteration's gate match (train(gate=True)).  Its low byte is 0xFE, elo_seed's 0x10 and a
+    sample_seed's the step, so it differs from every elo_seed and from every sample_seed of a step < 254."""
+    return (seed << 20) ^ (iteration << 8) ^ 0xFE
+
+
+def gate_verdict(winrate, threshold):
+    """eval.winrate >= WIN_RATE_THRESHOLD (training.rs:228): both are f32 there, so compared in float32."""
+    return bool(np.float32(winrate) >= np.float32(threshold))
+
+
+def agree_verdict(accepted, allgather):
+    """Every rank passes its one-byte verdict through allgather(bytes) -> [bytes per rank].  Returns
+    (rank 0's verdict, whether all ranks gave the same one): every rank acts on rank 0's, so the
+    trainers stay identical even if the ranks' matches were to differ."""
+    got = allgather(b"\x01" if accepted else b"\x00")
+    votes = [bytes(b) != b"\x00" for b in got]
+    return votes[0], all(v == votes[0] for v in votes)
+
+
 def shard_bounds(n, rank, world):
     """This rank's contiguous rows [lo, hi) of an n-row global batch."""
     return rank * n // world, (rank + 1) * n // world
 
 
-def _default_allgather():
+def _default_allgather(what="a shared replay buffer"):
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()):
-        raise ValueError("train: world > 1 with a shared replay buffer needs allgather= or an initialised "
-                         "torch.distributed group")
+        raise ValueError("train: world > 1 with %s needs allgather= or an initialised "
+                         "torch.distributed group" % what)
     from .dist import allgather_bytes
     return allgather_bytes
 
@@ -347,12 +401,13 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
           min_replay=MIN_REPLAY_SIZE, train_steps=NUM_TRAIN_STEPS, batch_size=BATCH_SIZE, replay=None, trainer=None,
           device=0, seed=SEED, dtype="f32", comm=None, shard_batch=None, reducer=None, shared_replay=None,
           allgather=None, log=None, log_batch=None, device_replay=False, elo_evaluator=None,
-          elo_games=EVALUATION_GAMES, elo_base=150.0):
+          elo_games=EVALUATION_GAMES, elo_base=150.0, gate=False, gate_threshold=WIN_RATE_THRESHOLD,
+          gate_games=EVALUATION_GAMES, log_gate=None, save_dir=None):
     """train() (training.rs:39-275) without the TUI.  Per iteration: self-play `games` games with
     model.valid() until the replay buffer holds min_replay unique positions, then train_steps AdamW
     steps on batches of batch_size at get_cyclical_lr(iteration); the new model replaces the old one.
-    The arena is off by default (SKIP_VALIDATION = true, parameters.rs:35); elo_evaluator, below,
-    turns on the Elo step.
+    The arena is off by default (SKIP_VALIDATION = true, parameters.rs:36); elo_evaluator and gate,
+    below, turn on the Elo step and the model gate.
 
     Data parallel (comm = (unique_id, rank, world) over RCCL, or reducer = (reduce, rank, world)
     through a host callback, Trainer.set_host_reducer): every rank plays its own games (seed offset
@@ -379,9 +434,25 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
     from the trainer and compute_elo_rankings([Player.base(elo_evaluator), Player.base(model)], elo_base,
     games=elo_games, engine=True, seed=elo_seed(seed, iteration)) plays its match in the engine arena
     (validation.Arena); the iteration's entry gains `elos`, `winrate_matrix`, `arena_avg_batch` and
-    `arena_s`.  Nothing else changes: the evaluator is not replaced and no model is rejected -- the
-    WIN_RATE_THRESHOLD gate (training.rs:208-232) needs a trainer that can take parameters back, an
-    entry point the library does not have.  Returns (trainer, replay, per-iteration stats)."""
+    `arena_s`.  Nothing else changes: the evaluator is not replaced.
+    gate (opt-in; False: every trained model is kept, as SKIP_VALIDATION = true): the model gate of
+    training.rs:131-132, 208-232.  Self-play runs on the incumbent net `model`, refreshed only when a
+    candidate is accepted (model.generation counts the accepts).  Each iteration takes trainer.snapshot()
+    before its first training step, trains as usual, brings a second net `candidate` up to date from the
+    trainer and plays evaluate(Player.base(candidate), Player.base(model), games=gate_games, engine=True,
+    seed=gate_seed(seed, iteration)); the candidate is kept when gate_verdict(winrate, gate_threshold).
+    log_gate(iteration, candidate, model, result, accepted) runs before anything is accepted or restored.
+    Accepted: model.update_from(trainer), then the Elo step (if elo_evaluator) and the checkpoints.
+    Rejected: trainer.restore() -- the parameters and running statistics go back to the snapshot, the
+    AdamW moments and step count stay (the reference's optimizer lives outside the loop) -- and the
+    iteration has no Elo step, no checkpoint and no `elos` key.  The entry gains `accepted`,
+    `gate_winrate`, `gate_p1`, `gate_draw`, `gate_p2`, `gate_avg_batch` and `gate_s`.  At world > 1 every
+    rank plays the same seeded match, the verdicts go through allgather (required then) and every rank
+    acts on rank 0's (agree_verdict); `gate_agree` records whether they were all equal.
+    save_dir (opt-in): the checkpoints of training.rs:253-270, written by rank 0 after an accepted
+    iteration (every iteration with the gate off): the model as iteration_{i}_elo_{elo:.0f}.mpk
+    (iteration_{i}.mpk without an elo_evaluator), and when iteration % 3 == 0 the replay buffer as
+    replay_buffer.  Returns (trainer, replay, per-iteration stats)."""
     from .memory import ReplayBuffer, add_from_ranks
     if comm and reducer:
         raise ValueError("train: comm (RCCL) or reducer (host), not both")
@@ -392,6 +463,8 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
         raise ValueError("shard_batch: batch_size %d is smaller than world %d" % (batch_size, world))
     if shared_replay and world > 1 and allgather is None:
         allgather = _default_allgather()
+    if gate and world > 1 and allgather is None:
+        allgather = _default_allgather("the model gate")
     # the largest shard a rank can get of a (possibly short) global batch
     local_batch = -(-batch_size // world) if shard_batch else batch_size
     if trainer is None:
@@ -406,10 +479,11 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
     elif device_replay and replay.device is None:
         raise ValueError("train: device_replay with a host-backed replay buffer")
     history = []
-    model = None
+    model = candidate = None
     for iteration in range(iterations):
         t0 = time.perf_counter()
-        model = trainer.model(dtype, into=model)   # created once, then refreshed in place on the device
+        if not gate or model is None:   # gate on: the incumbent, refreshed below when a candidate is accepted
+            model = trainer.model(dtype, into=model)   # created once, then refreshed in place on the device
         new_unique, plays, sims_done, games_done, steps_done, moves_done, finished = 0, 0, 0, 0, 0, 0, 0
         steps_global = 0
         while True:
@@ -446,6 +520,8 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
             if len(replay) >= min_replay:   # the global length when the buffer is shared
                 break
         t1 = time.perf_counter()
+        if gate:
+            trainer.snapshot()   # new_model = model.clone(), training.rs:132
         lr = get_cyclical_lr(iteration)
         pl_sum = vl_sum = 0.0
         for b in range(train_steps):
@@ -487,14 +563,43 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
               "games_finished": finished, "episode_steps": steps_done, "moves": moves_done,
               "shared_replay": shared_replay and world > 1, "shard_batch": shard_batch,
               "episode_steps_global": steps_global if shared_replay and world > 1 else steps_done}
-        if elo_evaluator is not None:
+        accepted, t3 = True, t2
+        if gate:   # training.rs:208-232
+            from .validation import Player, evaluate
+            candidate = trainer.model(dtype, into=candidate)
+            r = evaluate(Player.base(candidate), Player.base(model), games=gate_games, engine=True,
+                         seed=gate_seed(seed, iteration), device=device)
+            accepted = gate_verdict(r.winrate, gate_threshold)
+            if world > 1:   # every rank played the same match; all act on rank 0's verdict
+                accepted, st["gate_agree"] = agree_verdict(accepted, allgather)
+            st.update(accepted=accepted, gate_winrate=r.winrate, gate_p1=r.p1_winrate, gate_draw=r.drawrate,
+                      gate_p2=r.p2_winrate, gate_avg_batch=r.avg_batch_size, gate_s=time.perf_counter() - t2)
+            if log_gate:
+                log_gate(iteration, candidate, model, r, accepted)
+            if accepted:
+                model.update_from(trainer)   # model = new_model
+            else:
+                trainer.restore()            # the next iteration plays and trains from the old model
+            t3 = time.perf_counter()
+        if accepted and elo_evaluator is not None:
             from .validation import Player, compute_elo_rankings
-            model = trainer.model(dtype, into=model)
+            if not gate:
+                model = trainer.model(dtype, into=model)
             avg, elos, wm = compute_elo_rankings([Player.base(elo_evaluator), Player.base(model)], elo_base,
                                                  games=elo_games, engine=True, seed=elo_seed(seed, iteration),
                                                  device=device)
             st.update(elos=[float(e) for e in elos], winrate_matrix=wm, arena_avg_batch=avg,
-                      arena_s=time.perf_counter() - t2)
+                      arena_s=time.perf_counter() - t3)
+        if accepted and save_dir is not None and rank == 0:   # training.rs:253-270
+            import os
+            from .agent import save_mpk
+            os.makedirs(save_dir, exist_ok=True)
+            if iteration % 3 == 0:
+                replay.save(os.path.join(save_dir, "replay_buffer"))
+            name = "iteration_%d.mpk" % iteration
+            if elo_evaluator is not None:
+                name = "iteration_%d_elo_%.0f.mpk" % (iteration, st["elos"][-1])
+            save_mpk(os.path.join(save_dir, name), trainer.params(), trainer.blocks, trainer.filters)
         history.append(st)
         if log:
             log(st)

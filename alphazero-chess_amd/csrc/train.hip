@@ -1954,6 +1954,7 @@ struct Trainer {
     Layout L;
     size_t np = 0;
     float *p = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;
+    float* snap = nullptr;                   // az_trainer_snapshot's copy of p (allocated at the first snapshot)
     uint8_t* mask = nullptr;
     long long t = 0;                         // AdamW time (burn AdaptiveMomentumWState::time)
     int last_batch = 0;
@@ -3080,6 +3081,83 @@ int az_trainer_get_grads(az_trainer* t, float* out, size_t n) {
     AZ_HIP(hipStreamSynchronize(t->t->st));
     AZ_HIP(hipMemcpy(out, t->t->g, n * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
+}
+
+// p <- src (host or device memory) on the trainer's stream; returns with the stream idle.  The weight
+// buffers derived from p (wf, wd, uf, ud, the heads') are rebuilt by every trainer_grads, so p is all
+// there is to replace; m, v, g and the AdamW time are not touched.
+static int trainer_load_params(Trainer* T, const float* src, hipMemcpyKind kind) {
+    if (src != T->p) AZ_HIP(hipMemcpyAsync(T->p, src, T->np * sizeof(float), kind, T->st));
+    AZ_HIP(hipStreamSynchronize(T->st));
+    return 0;
+}
+
+int az_trainer_set_params(az_trainer* t, const float* weights, size_t n) {
+    if (!t) return fail("az_trainer_set_params: null trainer");
+    if (!weights) return fail("az_trainer_set_params: null weights");
+    Trainer* T = t->t;
+    if (n != T->np)
+        return fail("az_trainer_set_params: " + std::to_string(n) + " weights, the trainer has " + std::to_string(T->np));
+    AZ_HIP(hipSetDevice(T->device));
+    return trainer_load_params(T, weights, hipMemcpyHostToDevice);
+}
+
+int az_trainer_set_params_device(az_trainer* t, const float* d_weights, size_t n, void* stream) {
+    if (!t) return fail("az_trainer_set_params_device: null trainer");
+    if (!d_weights) return fail("az_trainer_set_params_device: null weights");
+    Trainer* T = t->t;
+    if (n != T->np)
+        return fail("az_trainer_set_params_device: " + std::to_string(n) + " weights, the trainer has " +
+                    std::to_string(T->np));
+    AZ_HIP(hipSetDevice(T->device));
+    if (stream && (hipStream_t)stream != T->st) {   // the copy waits for what the caller's stream holds
+        hipEvent_t e = nullptr;
+        AZ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        hipError_t rc = hipEventRecord(e, (hipStream_t)stream);
+        if (rc == hipSuccess) rc = hipStreamWaitEvent(T->st, e, 0);
+        (void)hipEventDestroy(e);                   // released once the wait has passed it
+        if (rc != hipSuccess) return fail(std::string("az_trainer_set_params_device: ") + hipGetErrorString(rc));
+    }
+    return trainer_load_params(T, d_weights, hipMemcpyDeviceToDevice);
+}
+
+int az_trainer_snapshot(az_trainer* t) {
+    if (!t) return fail("az_trainer_snapshot: null trainer");
+    Trainer* T = t->t;
+    AZ_HIP(hipSetDevice(T->device));
+    float* s = T->snap;
+    if (!s && !(s = T->alloc(T->np))) {
+        (void)hipGetLastError();
+        return fail("az_trainer_snapshot: out of device memory");
+    }
+    AZ_HIP(hipMemcpyAsync(s, T->p, T->np * sizeof(float), hipMemcpyDeviceToDevice, T->st));
+    AZ_HIP(hipStreamSynchronize(T->st));
+    T->snap = s;
+    return 0;
+}
+
+int az_trainer_restore(az_trainer* t) {
+    if (!t) return fail("az_trainer_restore: null trainer");
+    Trainer* T = t->t;
+    if (!T->snap) return fail("az_trainer_restore: no snapshot taken (az_trainer_snapshot)");
+    AZ_HIP(hipSetDevice(T->device));
+    return trainer_load_params(T, T->snap, hipMemcpyDeviceToDevice);
+}
+
+int az_trainer_get_snapshot(az_trainer* t, float* out, size_t n) {
+    if (!t) return fail("az_trainer_get_snapshot: null trainer");
+    Trainer* T = t->t;
+    if (!out || n != T->np) return fail("az_trainer_get_snapshot: bad arguments");
+    if (!T->snap) return fail("az_trainer_get_snapshot: no snapshot taken (az_trainer_snapshot)");
+    AZ_HIP(hipSetDevice(T->device));
+    AZ_HIP(hipStreamSynchronize(T->st));
+    AZ_HIP(hipMemcpy(out, T->snap, n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int64_t az_trainer_adamw_steps(az_trainer* t) {
+    if (!t) return fail("az_trainer_adamw_steps: null trainer");
+    return t->t->t;
 }
 
 int az_net_update_from_trainer(az_net* net, az_trainer* t) {

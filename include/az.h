@@ -349,6 +349,25 @@ int az_trainer_step(az_trainer* t, const float* planes, const float* target_poli
 /* flat parameters (to build an az_net for self-play, or to save) / last gradients */
 int az_trainer_get_params(az_trainer* t, float* out, size_t n);
 int az_trainer_get_grads(az_trainer* t, float* out, size_t n);
+/* Replace the trainer's flat parameters (az_net_num_params layout, BatchNorm running statistics
+ * included).  The AdamW moments, the AdamW step count, the last gradients and every setting (comm,
+ * reducer, sharded) stay as they are.  n must be the trainer's parameter count, else an error and
+ * no change.  Not a collective: at world > 1 the caller makes the same call on every rank. */
+int az_trainer_set_params(az_trainer* t, const float* weights, size_t n);
+/* the same from device memory on the trainer's device, ordered after what `stream` holds (NULL: the
+ * trainer's stream); returns when the parameters are in place */
+int az_trainer_set_params_device(az_trainer* t, const float* d_weights, size_t n, void* stream);
+/* new_model = model.clone() (training.rs:132) kept on the device: copy the current parameters into a
+ * trainer-owned buffer (allocated at the first call: one more copy of the parameters in HBM, freed with
+ * the trainer; if that fails, an error and no change).  A later snapshot overwrites it. */
+int az_trainer_snapshot(az_trainer* t);
+/* parameters <- the snapshot (the rejected branch of training.rs:231); everything else as
+ * az_trainer_set_params leaves it.  An error, and no change, before the first snapshot. */
+int az_trainer_restore(az_trainer* t);
+/* test hook: the snapshot's contents; an error before the first snapshot */
+int az_trainer_get_snapshot(az_trainer* t, float* out, size_t n);
+/* optimizer steps applied so far (burn's AdaptiveMomentumWState::time) */
+int64_t az_trainer_adamw_steps(az_trainer* t);
 /* az_net_update_device from the trainer's device parameters (BatchNorm running statistics included),
  * after everything queued on the trainer's stream: device to device, nothing goes to the host.  The
  * trainer and the net must share the device and the blocks x filters shape. */
