@@ -216,6 +216,16 @@ SIGNATURES = [
     ("az_arena_history", C.c_int, [C.c_void_p, C.c_int, P(C.c_int32), C.c_int]),
     ("az_arena_stats", C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
     ("az_arena_choose", C.c_int, [P(C.c_float), C.c_int, C.c_int, C.c_float]),
+    ("az_tournament_matches", C.c_int, [C.c_int]),
+    ("az_tournament_pair", C.c_int, [C.c_int, C.c_int, P(C.c_int), P(C.c_int)]),
+    ("az_tournament_create", C.c_int, [P(AzArenaPlayer), C.c_int, P(AzArenaCfg), C.c_int, P(C.c_void_p)]),
+    ("az_tournament_destroy", C.c_int, [C.c_void_p]),
+    ("az_tournament_reset", C.c_int, [C.c_void_p, P(AzPos), C.c_uint64]),
+    ("az_tournament_step", C.c_int, [C.c_void_p, P(C.c_float), P(C.c_int)]),
+    ("az_tournament_results", C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32)]),
+    ("az_tournament_live", C.c_int, [C.c_void_p, P(C.c_int32)]),
+    ("az_tournament_history", C.c_int, [C.c_void_p, C.c_int, C.c_int, P(C.c_int32), C.c_int]),
+    ("az_tournament_stats", C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -19,6 +19,10 @@ out of scope; Player.external() is its seat in the engine arena (the caller supp
 `Arena` is the same match with its games in HBM (libaz az_arena_*: one az_arena_step per ply, move
 generation, choice, play_move and the histories on the device); evaluate(..., engine=True) plays through
 it with the same seeded uniforms and returns the same moves, results and statistics.
+`Tournament` is a whole round robin in one handle (libaz az_tournament_*): every pairing of a pool advances
+in lockstep and each player evaluates all of its games to move at once; evaluate_round_robin and
+compute_elo_rankings(..., engine=True, tournament=True) play through it and return the pairwise matches' moves,
+results and rates.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -181,6 +185,120 @@ class Arena:
         return a.value, b.value
 
 
+def tournament_matches(n_players):
+    """az_tournament_pair's order (ratings.rs:10-11): [(i, j)] with j < i; players[i] is player_1 of its match."""
+    n = L.check(L.lib.az_tournament_matches(int(n_players)))
+    out = []
+    for m in range(n):
+        i, j = C.c_int(), C.c_int()
+        L.check(L.lib.az_tournament_pair(int(n_players), m, C.byref(i), C.byref(j)))
+        out.append((i.value, j.value))
+    return out
+
+
+class Tournament:
+    """az_tournament: every pairing of `players` as one match of `games` games, all in HBM and advancing in
+    lockstep; step() plays one ply of every live game of every match, each player evaluating all of its
+    games to move at once.  Every game comes out as Arena(players[i], players[j], ...) plays it."""
+
+    def __init__(self, players, games=EVALUATION_GAMES, sims=NUM_SIMULATIONS,
+                 num_stochastic_moves=TEMPERATURE_ANNEALING, seed=0, device=0, c_puct=C_PUCT):
+        self.games = games
+        self._players = list(players)                 # keeps the nets alive as long as the handle
+        self.matches = tournament_matches(len(self._players))
+        recs = (L.AzArenaPlayer * len(self._players))()
+        for k, p in enumerate(self._players):
+            net = p.model._h if p.kind in ("mcts", "base") and p.model is not None else None
+            recs[k] = L.AzArenaPlayer(_KINDS[p.kind], net, int(p.depth or 0))
+        cfg = L.AzArenaCfg(games, sims, num_stochastic_moves, c_puct, seed)
+        h = C.c_void_p()
+        L.check(L.lib.az_tournament_create(recs, len(self._players), C.byref(cfg), device, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            L.lib.az_tournament_destroy(self._h)
+        except Exception:
+            pass
+
+    def reset(self, start=None, seed=0):
+        """Every game of every match back to live; start: `games` Positions (or an az_pos array) -- start[g]
+        opens game g of every match -- None = the start position."""
+        st = None
+        if start is not None:
+            arr = start if isinstance(start, np.ndarray) else positions_to_array(start)
+            arr = np.ascontiguousarray(arr, L.POS_DTYPE)
+            assert len(arr) == self.games
+            st = arr.ctypes.data_as(C.POINTER(L.AzPos))
+        L.check(L.lib.az_tournament_reset(self._h, st, int(seed)))
+
+    def step(self, u=None):
+        """One ply of every live game; u [matches, games] float32 uniforms (None: the engine's stream).
+        Returns the number of games still going."""
+        up = None
+        if u is not None:
+            u = np.ascontiguousarray(u, np.float32)
+            assert u.size == len(self.matches) * self.games
+            up = L.fptr(u)
+        live = C.c_int()
+        L.check(L.lib.az_tournament_step(self._h, up, C.byref(live)))
+        return live.value
+
+    def results(self):
+        """(result [matches, games]: ONGOING / DRAW / WHITE_WINS / BLACK_WINS, plies [matches, games])"""
+        res = np.zeros((len(self.matches), self.games), np.int32)
+        plies = np.zeros((len(self.matches), self.games), np.int32)
+        L.check(L.lib.az_tournament_results(self._h, L.i32ptr(res), L.i32ptr(plies)))
+        return res, plies
+
+    def live(self):
+        """bool [matches, games]: the games still going, as the last step read them back (no device access)."""
+        out = np.zeros((len(self.matches), self.games), np.int32)
+        L.check(L.lib.az_tournament_live(self._h, L.i32ptr(out)))
+        return out != 0
+
+    def history(self, match, game):
+        out = np.zeros(512, np.int32)
+        n = L.check(L.lib.az_tournament_history(self._h, int(match), int(game), L.i32ptr(out), out.size))
+        return [int(a) for a in out[:n]]
+
+    def stats(self):
+        """(num_inferences, rows) of the whole tournament since the last reset."""
+        a, b = C.c_double(), C.c_double()
+        L.check(L.lib.az_tournament_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
+def tiled_uniforms(seed, games, ply, matches):
+    """[matches, games] float32: choice_uniform(seed, g, ply) depends on the game within its match only, so
+    one draw per game serves every match."""
+    row = np.array([choice_uniform(seed, g, ply) for g in range(games)], np.float32)
+    return np.tile(row, (matches, 1))
+
+
+def evaluate_round_robin(players, games=EVALUATION_GAMES, sims=NUM_SIMULATIONS,
+                         num_stochastic_moves=TEMPERATURE_ANNEALING, seed=0, device=0, max_plies=1000, record=False):
+    """Every pairing of `players` through one Tournament, with the per-(game, ply) uniforms of
+    evaluate(engine=True).  Returns, per match in Tournament.matches order, what
+    evaluate(players[i], players[j], ..., record=record) returns: the same move lists, results and rate fields.
+    num_inferences and avg_batch_size are the WHOLE tournament's in every entry (a player's forward serves
+    all of its matches at once, so they cannot be attributed to one match)."""
+    tour = Tournament(players, games=games, sims=sims, num_stochastic_moves=num_stochastic_moves, seed=seed,
+                      device=device)
+    M = len(tour.matches)
+    for ply in range(max_plies):
+        if tour.step(tiled_uniforms(seed, games, ply, M)) == 0:
+            break
+    res, _ = tour.results()
+    num_inferences, rows = tour.stats()
+    out = []
+    for m in range(M):
+        result = [{L.DRAW: 0, L.WHITE_WINS: 1, L.BLACK_WINS: -1}.get(int(r)) for r in res[m]]
+        hist = [tour.history(m, g) for g in range(games)] if record else None
+        out.append(_evaluation_result(result, games, num_inferences, rows, hist, record))
+    return out
+
+
 def arena_choose(policy, fullmoves, num_stochastic_moves, u):
     """az_arena_choose: `choose` in libaz (the rule the arena kernels apply)."""
     p = np.ascontiguousarray(policy, np.float32)
@@ -322,11 +440,23 @@ def compute_elos(winrate_matrix, base_elo):
     return elos
 
 
-def compute_elo_rankings(players, base_elo=150.0, **kw):
+def compute_elo_rankings(players, base_elo=150.0, tournament=False, **kw):
     """ratings.rs:5-28: round robin, winrate matrix, Elo.  Returns (avg_batch_size, elos, matrix).
-    Keywords go to evaluate (engine=True: every match through the engine arena)."""
+    Keywords go to evaluate (engine=True: every match through the engine arena).  tournament=True (needs
+    engine=True): all matches through one Tournament (evaluate_round_robin) -- the same matrix and Elos;
+    the average batch is the tournament's rows / num_inferences."""
     n = len(players)
     wm = [[0.5] * n for _ in range(n)]
+    if tournament:
+        kw = dict(kw)
+        if not kw.pop("engine", False):
+            raise ValueError("compute_elo_rankings: tournament=True plays on the device; pass engine=True")
+        kw.pop("record", None)
+        res = evaluate_round_robin(players, **kw)
+        for (i, j), r in zip(tournament_matches(n), res):
+            wm[j][i] = 1.0 - r.winrate
+            wm[i][j] = r.winrate
+        return res[0].avg_batch_size, compute_elos(wm, base_elo), wm
     ninf, avg = 0.0, 0.0
     for i in range(n):
         for j in range(i):

@@ -14,6 +14,8 @@
 //   k_arena_commit  one wavefront per game, only if every choice was valid: play_move (chess.rs:36-63)
 //                   -- play, outcome(), repetition against the game's position history, the 50-move
 //                   and 200-fullmove limits -- and the appends to the histories
+// The bodies of pick and commit are arena_dev.h's arena_pick and arena_commit, which the tournament arena
+// (tournament.hip) calls too.
 // The host keeps what the composed players need: an MCTS player's games go through the existing
 // az_search (fresh noiseless roots from a host copy of the move lists), a MiniMax player's through
 // az_minimax_scores on the downloaded positions; both come back as given actions.
@@ -22,14 +24,11 @@
 #include <string>
 #include <vector>
 
-#include "az_internal.h"
-#include "search_dev.h"
+#include "arena_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace azi {
-
-enum { ST_OK = 0, ST_ILLEGAL = 1, ST_NONFINITE = 2 };
 
 // device state, passed by value.  io is one block the host reads back per step:
 // [0] any bad choice, [1] live games after the ply, then status [G], chosen [G], result [G]
@@ -48,8 +47,6 @@ struct ArenaDev {
     __device__ __host__ int* chosen() const { return io + 2 + G; }
     __device__ __host__ int* result() const { return io + 2 + 2 * G; }
 };
-
-__device__ __forceinline__ bool non_finite(float w) { return (azc::f2u(w) & 0x7f800000u) == 0x7f800000u; }
 
 __global__ void __launch_bounds__(64) k_arena_reset(ArenaDev A, const azc::Pos* __restrict__ start) {
     const int g = blockIdx.x * 64 + threadIdx.x;
@@ -86,92 +83,16 @@ __global__ void __launch_bounds__(64) k_arena_stage(ArenaDev A, int slot, float*
 }
 
 __global__ void __launch_bounds__(64) k_arena_pick(ArenaDev A) {
-    __shared__ Edge s_ed[MAX_EDGES];
-    __shared__ float s_w[MAX_EDGES];
-    __shared__ float s_sw[MAX_EDGES];
-    __shared__ uint16_t s_si[MAX_EDGES];
-    __shared__ int s_a;
+    __shared__ PickShared S;
     const int g = vgpr_index(blockIdx.x), lane = threadIdx.x;
     if (g >= A.G) return;
     const int slot = A.tomove[g];
     if (slot < 0) return;
-    azc::Pos p = A.poshist[(size_t)g * HMAX + A.plies[g]];
+    const azc::Pos p = A.poshist[(size_t)g * HMAX + A.plies[g]];
     const int kind = slot ? A.kind1 : A.kind0;
-    int n = 0;
-    leaf_rules<1>(p, s_ed, lane, &n);
-    __syncthreads();
-    const float u = A.u[g];
-    int action = -1, st = ST_OK;
-    if (kind == AZ_PLAYER_BASE) {
-        const float* pol = (slot ? A.pol1 : A.pol0) + (size_t)A.row[g] * AZ_ACTION_SPACE;
-        bool bad = false;
-        float bw = -1.0f;
-        int bi = -1;
-        for (int e = lane; e < n; e += 64) {
-            const int ii = s_ed[e].idx & azc::IDX_MASK;
-            const float w = pol[ii];
-            s_w[e] = w;
-            bad |= non_finite(w);
-            if (w > bw || (w == bw && ii > bi)) { bw = w; bi = ii; }
-        }
-        if (__ballot(bad)) {
-            st = ST_NONFINITE;
-        } else if ((int)p.fullmoves > A.nsm) {               // validation.rs:297: the LAST maximal index
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ow = __shfl_xor(bw, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (ow > bw || (ow == bw && oi > bi)) { bw = ow; bi = oi; }
-            }
-            action = bw > 0.0f ? bi : AZ_ACTION_SPACE - 1;   // an all-zero row's last maximum is entry 4095
-        } else {                                             // WeightedIndex: ascending index order
-            __syncthreads();
-            for (int e = lane; e < n; e += 64) {
-                const int ii = s_ed[e].idx & azc::IDX_MASK;
-                int r = 0;
-                for (int f = 0; f < n; f++) r += (s_ed[f].idx & azc::IDX_MASK) < ii;
-                s_si[r] = (uint16_t)ii;
-                s_sw[r] = s_w[e];
-            }
-            __syncthreads();
-            if (lane == 0) {
-                float total = 0.0f;
-                for (int r = 0; r < n; r++) total = total + s_sw[r];
-                float x = u * total;
-                if (!(x < total)) x = nextafterf(total, 0.0f);
-                float cw = 0.0f;
-                int a = AZ_ACTION_SPACE - 1;                 // no cumulative weight above x: the last entry
-                for (int r = 0; r < n; r++) {
-                    cw = cw + s_sw[r];
-                    if (cw > x) { a = s_si[r]; break; }
-                }
-                s_a = a;
-            }
-            __syncthreads();
-            action = s_a;
-        }
-    } else if (kind == AZ_PLAYER_RANDOM) {                   // entry min(floor(u n), n - 1) of the list
-        if (lane == 0) {                                     // with its under-promotion duplicates
-            int tot = 0;
-            for (int e = 0; e < n; e++) tot += (s_ed[e].idx & azc::PROMO_FLAG) ? 4 : 1;
-            int k = (int)floorf(u * (float)tot);
-            k = k < tot - 1 ? k : tot - 1;
-            int a = -1, acc = 0;
-            for (int e = 0; e < n; e++) {
-                acc += (s_ed[e].idx & azc::PROMO_FLAG) ? 4 : 1;
-                if (k < acc) { a = s_ed[e].idx & azc::IDX_MASK; break; }
-            }
-            s_a = a;
-        }
-        __syncthreads();
-        action = s_a;
-    } else {
-        action = A.actions[g];
-    }
-    if (st == ST_OK) {
-        bool hit = false;
-        for (int e = lane; e < n; e += 64) hit |= (s_ed[e].idx & azc::IDX_MASK) == action;
-        if (!__ballot(hit)) st = ST_ILLEGAL;
-    }
+    const float* pol = kind == AZ_PLAYER_BASE ? (slot ? A.pol1 : A.pol0) + (size_t)A.row[g] * AZ_ACTION_SPACE : nullptr;
+    int st;
+    const int action = arena_pick(S, p, kind, pol, A.u[g], A.actions[g], A.nsm, lane, &st);
     if (lane == 0) {
         A.chosen()[g] = action;
         A.status()[g] = st;
@@ -185,33 +106,13 @@ __global__ void __launch_bounds__(64) k_arena_commit(ArenaDev A) {
     if (g >= A.G || load_fresh(&A.io[0]) != 0) return;       // all or nothing
     if (A.tomove[g] < 0) return;
     const int k = A.plies[g];
-    azc::Pos* hist = A.poshist + (size_t)g * HMAX;
-    const azc::Pos p = hist[k];
-    const int action = A.chosen()[g];
-    azc::Pos c = azc::play_index(p, action);
-    int n = 0;
-    int res = leaf_rules<1>(c, s_ed, lane, &n);              // outcome() first (chess.rs:43-50)
-    if (res == azc::ONGOING) {
-        // the position enters the multiset, then the draws (chess.rs:52-60): equal positions lie an
-        // even number d <= halfmoves of plies back -- one candidate per lane
-        const int hm = c.halfmoves;
-        int cnt = 0;
-        for (int d0 = 2; d0 <= hm; d0 += 128) {
-            const int d = d0 + 2 * lane;
-            bool eq = false;
-            if (d <= hm && k + 1 - d >= 0) eq = azc::chess_eq(hist[k + 1 - d], c);
-            cnt += __popcll(__ballot(eq));
-        }
-        if (cnt + 1 >= azc::REPETITIONS || c.halfmoves >= azc::NUM_HALFMOVES || c.fullmoves >= azc::NUM_FULLMOVES ||
-            k + 1 >= HMAX)
-            res = azc::DRAW;
-    }
+    int turn;
+    const int res = arena_commit(s_ed, A.poshist + (size_t)g * HMAX, A.moves + (size_t)g * HMAX, k, A.chosen()[g], lane,
+                                 &turn);
     if (lane == 0) {
-        if (k + 1 < HMAX) hist[k + 1] = c;
-        if (k < HMAX) A.moves[(size_t)g * HMAX + k] = action;
         A.plies[g] = k + 1;
         A.result()[g] = res;
-        A.tomove[g] = res != azc::ONGOING ? -1 : (A.same ? 0 : ((c.turn ^ g) & 1));
+        A.tomove[g] = res != azc::ONGOING ? -1 : (A.same ? 0 : ((turn ^ g) & 1));
         if (res == azc::ONGOING) atomicAdd(&A.io[1], 1);
     }
 }

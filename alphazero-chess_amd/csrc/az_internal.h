@@ -315,3 +315,10 @@ double net_tower_flop_per_eval(int blocks, int filters);
 }  // namespace azi
 
 struct az_net { azi::NetDev* dev; };
+
+namespace azi {
+// search.hip: az_search_run with the improved policy left in device memory, d_improved [games][4096] on
+// the search's device -- the simulations of the roots just set, then k_readout.  Complete on return.
+// *evals (may be nullptr): the network rows the search has evaluated since it was created
+int search_run_device(az_search* s, float* d_improved, unsigned long long* evals);
+}  // namespace azi

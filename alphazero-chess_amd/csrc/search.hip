@@ -1229,3 +1229,25 @@ int az_search_timing(az_search* s, az_timing* out, int reset, int enable) {
 }
 
 }  // extern "C"
+
+// az_search_run for a caller that keeps the result on the device (tournament.hip): the simulations of the
+// roots just set, then k_readout's improved policy into d_improved [games][4096] (device memory of the
+// search's device).  Complete on return.  *evals (optional): network rows since the search was created.
+int azi::search_run_device(az_search* s, float* d_improved, unsigned long long* evals) {
+    if (!s || !d_improved) return fail("search_run_device: null argument");
+    if (check_net_generation(s, "search_run_device")) return -1;
+    if (!s->roots_fresh) return fail("search_run_device: set roots first");
+    s->roots_fresh = false;
+    AZ_HIP(hipSetDevice(s->device));
+    int rc = run_sims(s);
+    if (rc) return rc;
+    k_readout<<<s->E.G, 256, 0, s->st>>>(s->E, d_improved, nullptr, nullptr);
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipStreamSynchronize(s->st));
+    if (evals) {
+        Counters c;
+        AZ_HIP(hipMemcpy(&c, s->E.ctr, sizeof(c), hipMemcpyDeviceToHost));
+        *evals = c.evals + sum_games(s, s->E.g_evals);
+    }
+    return 0;
+}

@@ -591,6 +591,50 @@ int az_arena_stats(az_arena* a, double* num_inferences, double* rows);
  * whose cumulative sum exceeds x, 4095 if none does */
 int az_arena_choose(const float* policy, int fullmoves, int num_stochastic_moves, float u);
 
+/* ---- tournament arena: the pairings of a round robin (ratings.rs:10-24) in one device handle ------
+ * Every pairing of a pool of players is one az_arena match of cfg->games games; all matches advance in
+ * lockstep and each player evaluates all of its games to move at once.  Match m = i (i - 1) / 2 + j for
+ * 0 <= j < i < n_players is evaluate(&players[i], &players[j]): players[i] is its player 1.  Tournament
+ * game t = m * games + g is game g of match m; player 1 is White in it when g is even.  Every game comes
+ * out move for move as az_arena plays it. */
+#define AZ_TOURNAMENT_MAX_PLAYERS 16
+typedef struct az_tournament az_tournament;
+/* n (n - 1) / 2, < 0 outside 2..AZ_TOURNAMENT_MAX_PLAYERS.  No handle, no device. */
+int az_tournament_matches(int n_players);
+/* *p1 = i, *p2 = j of match m in the order above.  No handle, no device. */
+int az_tournament_pair(int n_players, int m, int* p1, int* p2);
+/* players [n_players]: MCTS, BASE, MINIMAX and RANDOM (EXTERNAL is refused); two entries naming the same
+ * net are two players.  Per mover kind and ply, over all of the player's games to move in all its matches:
+ *   BASE      one forward of its games' planes (rows ascending in t), then az_arena_choose's rule on the
+ *             device; num_inferences += 1, rows += games to move
+ *   MCTS      one search of (n_players - 1) * ((games + 1) / 2) slots (noiseless, no FEN cache, cfg->seed;
+ *             spare slots repeat its first root) whose improved policy stays on the device, then the same
+ *             rule; num_inferences += sims + 1, rows += the search's evaluations
+ *   MINIMAX   one az_minimax_scores call, then az_minimax_best with the game's uniform
+ *   RANDOM    as in az_arena
+ * Arguments are checked before the first device call.  The handle starts reset with cfg->seed. */
+int az_tournament_create(const az_arena_player* players, int n_players, const az_arena_cfg* cfg, int device,
+                         az_tournament** out);
+int az_tournament_destroy(az_tournament* t);
+/* start [games]: start[g] is the start position of game g of EVERY match, NULL = the start position;
+ * validated as az_arena_reset does (a rejected or already decided position is an error, and so is, with
+ * an MCTS player in the pool, a set that puts one side to move in more than (games + 1) / 2 games of a
+ * match); nothing changes on an error. */
+int az_tournament_reset(az_tournament* t, const az_pos* start, uint64_t seed);
+/* one ply of every live game of every match.  u [matches * games]: u[t] is game t's uniform; NULL: the
+ * engine's stream, stream_key(seed, g, ply, 2) with g the game within its match -- the stream of
+ * az_arena handles created with the same seed.  *live = games still going.  All or nothing across the
+ * tournament: a refused move or a non-finite legal policy entry fails the call with a message naming the
+ * match and the game, and no game of any match has advanced. */
+int az_tournament_step(az_tournament* t, const float* u, int* live);
+/* [matches * games] each, either may be NULL */
+int az_tournament_results(az_tournament* t, int32_t* result, int32_t* plies);
+/* live [matches * games] from the host mirror: no device access.  Returns the number of live games. */
+int az_tournament_live(az_tournament* t, int32_t* live);
+int az_tournament_history(az_tournament* t, int match, int game, int32_t* moves, int cap);
+/* forwards launched and rows evaluated by the whole tournament since the last reset */
+int az_tournament_stats(az_tournament* t, double* num_inferences, double* rows);
+
 #ifdef __cplusplus
 }
 #endif
