@@ -67,6 +67,26 @@ class SelfPlay:
         self.search.check(L.lib.az_selfplay_run_sims(self.search._h, int(nsims), C.byref(fin), C.byref(act), C.byref(done)))
         return fin.value, act.value, bool(done.value)
 
+    def adopt(self):
+        """az_selfplay_adopt_net: between two moves, after the model was updated in place (or a
+        caller-owned evaluator's model changed), carry the games in flight over to the new weights:
+        every live root is evaluated again and re-noised from its (seed, game id, ply) stream, the
+        start-position template of continuous mode too; histories, ids, plies and the steps recorded so
+        far stay.  A no-op for a net whose generation has not moved."""
+        self.search.check(L.lib.az_selfplay_adopt_net(self.search._h))
+
+    def inflight(self):
+        """The games now in the slots: [(slot, game_id, ply, active, [moves played so far])]."""
+        G, h = self.games, self.search._h
+        gid, ply, act = np.zeros(G, np.int32), np.zeros(G, np.int32), np.zeros(G, np.int32)
+        off = np.zeros(G + 1, np.int32)
+        n = L.check(L.lib.az_selfplay_inflight(h, None, None, None, None, None, 0))
+        moves = np.zeros(max(n, 1), np.int32)
+        L.check(L.lib.az_selfplay_inflight(h, L.i32ptr(gid), L.i32ptr(ply), L.i32ptr(act), L.i32ptr(moves),
+                                           L.i32ptr(off), moves.size))
+        return [(g, int(gid[g]), int(ply[g]), bool(act[g]), [int(m) for m in moves[off[g]:off[g + 1]]])
+                for g in range(G)]
+
     def drain(self):
         return [_convert(s) for s in self.drain_raw()]
 
@@ -402,7 +422,8 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
           device=0, seed=SEED, dtype="f32", comm=None, shard_batch=None, reducer=None, shared_replay=None,
           allgather=None, log=None, log_batch=None, device_replay=False, elo_evaluator=None,
           elo_games=EVALUATION_GAMES, elo_base=150.0, gate=False, gate_threshold=WIN_RATE_THRESHOLD,
-          gate_games=EVALUATION_GAMES, log_gate=None, save_dir=None):
+          gate_games=EVALUATION_GAMES, log_gate=None, save_dir=None, carry_games=False, games_per_iteration=None,
+          log_selfplay=None, log_adopt=None):
     """train() (training.rs:39-275) without the TUI.  Per iteration: self-play `games` games with
     model.valid() until the replay buffer holds min_replay unique positions, then train_steps AdamW
     steps on batches of batch_size at get_cyclical_lr(iteration); the new model replaces the old one.
@@ -452,11 +473,31 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
     save_dir (opt-in): the checkpoints of training.rs:253-270, written by rank 0 after an accepted
     iteration (every iteration with the gate off): the model as iteration_{i}_elo_{elo:.0f}.mpk
     (iteration_{i}.mpk without an elo_evaluator), and when iteration % 3 == 0 the replay buffer as
-    replay_buffer.  Returns (trainer, replay, per-iteration stats)."""
+    replay_buffer.
+    carry_games (opt-in; False: the lockstep passes above, untouched): self-play games straddle the weight
+    updates.  ONE SelfPlay(model, games, sims, continuous=True, seed=seed + 1000003 * rank) is created
+    before the first iteration, reset once and kept for the whole run: `games` slots that are always full.
+    A pass plays moves until at least games_per_iteration (default: games) more games have finished in it,
+    and passes repeat until the buffer holds min_replay positions -- an iteration is counted by games
+    finished, not games started.  At the top of every later iteration, after the model was refreshed in
+    place, sp.adopt() carries the games in flight over to the new weights (SelfPlay.adopt: a game's plies
+    before it are the old net's, every ply from it on equals a fresh search of that history on the new net;
+    with the gate on and a rejected candidate the generation has not moved and it does nothing), then
+    log_adopt(iteration, sp.inflight(), trainer) runs.  log_selfplay(iteration, drained) runs for every
+    non-empty drain.  The entry gains `carried_in` (games in flight at the iteration's start with at least
+    one move played under earlier weights; 0 in iteration 0), `adopt_s` and `selfplay_avg_batch` (network
+    rows per simulation step of the iteration's self-play); `selfplay_games` is the number of games that
+    finished in the iteration.  Games still in flight when train() returns are dropped: their steps reach
+    neither the buffer nor the caller, and the return shape does not change.  One rank only for now
+    (world > 1 raises ValueError); device_replay, elo_evaluator, gate, save_dir and dtype combine with it
+    unchanged.
+    Returns (trainer, replay, per-iteration stats)."""
     from .memory import ReplayBuffer, add_from_ranks
     if comm and reducer:
         raise ValueError("train: comm (RCCL) or reducer (host), not both")
     rank, world = (comm[1], comm[2]) if comm else (reducer[1], reducer[2]) if reducer else (0, 1)
+    if carry_games and world > 1:
+        raise ValueError("carry_games: one rank for now")
     shard_batch = world > 1 if shard_batch is None else bool(shard_batch)
     shared_replay = world > 1 if shared_replay is None else bool(shared_replay)
     if shard_batch and batch_size < world:
@@ -480,13 +521,49 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
         raise ValueError("train: device_replay with a host-backed replay buffer")
     history = []
     model = candidate = None
+    carried = None                      # carry_games: the one continuous SelfPlay of the run
+    carry_target = games if games_per_iteration is None else int(games_per_iteration)
     for iteration in range(iterations):
         t0 = time.perf_counter()
         if not gate or model is None:   # gate on: the incumbent, refreshed below when a candidate is accepted
             model = trainer.model(dtype, into=model)   # created once, then refreshed in place on the device
         new_unique, plays, sims_done, games_done, steps_done, moves_done, finished = 0, 0, 0, 0, 0, 0, 0
         steps_global = 0
-        while True:
+        carry = {}
+        if carry_games:
+            ta = time.perf_counter()
+            if carried is None:
+                carried = SelfPlay(model, games=games, sims=sims, device=device, continuous=True,
+                                   seed=seed + 1000003 * rank)
+                carried.reset()
+                carry = {"carried_in": 0, "adopt_s": 0.0}
+            else:
+                carried.adopt()
+                flight = carried.inflight()
+                carry = {"carried_in": sum(1 for _, _, ply, active, _ in flight if active and ply > 0),
+                         "adopt_s": time.perf_counter() - ta}
+                if log_adopt:
+                    log_adopt(iteration, flight, trainer)
+            s0 = carried.search.stats()   # after the adoption: its root rows are not self-play batches
+        while carry_games:              # passes of the carried pool (the lockstep passes are the loop below)
+            done = 0
+            while done < carry_target:
+                fin, _ = carried.step()
+                done += fin
+                drained = carried.drain_raw()
+                if len(drained):
+                    steps_done += len(drained)
+                    new_unique += replay.add_many(drained)
+                    if log_selfplay:
+                        log_selfplay(iteration, drained)
+            plays += 1
+            if len(replay) >= min_replay:
+                ss = carried.search.stats()
+                sims_done, moves_done = ss["sims"] - s0["sims"], ss["moves"] - s0["moves"]
+                finished = games_done = ss["games_finished"] - s0["games_finished"]
+                carry["selfplay_avg_batch"] = (ss["evals"] - s0["evals"]) / max(sims_done / games, 1)
+                break
+        while not carry_games:
             sp = SelfPlay(model, games=games, sims=sims, device=device, continuous=False,
                           seed=seed + 1000003 * rank + 7919 * iteration + 104729 * plays)
             sp.reset()
@@ -563,6 +640,7 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
               "games_finished": finished, "episode_steps": steps_done, "moves": moves_done,
               "shared_replay": shared_replay and world > 1, "shard_batch": shard_batch,
               "episode_steps_global": steps_global if shared_replay and world > 1 else steps_done}
+        st.update(carry)
         accepted, t3 = True, t2
         if gate:   # training.rs:208-232
             from .validation import Player, evaluate

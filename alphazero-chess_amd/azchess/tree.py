@@ -117,6 +117,13 @@ class BatchedSearch:
         self.check(L.lib.az_search_advance(self._h, L.i32ptr(a), 1 if apply_noise else 0, L.i32ptr(res)))
         return res
 
+    def adopt(self, apply_noise=False):
+        """az_search_adopt_net: after the model was updated in place (or a caller-owned evaluator's
+        model changed), rebuild every active root on the new weights -- the state set_roots would give
+        from the game's history, game id and noise ply -- so that run() is valid again.  Inactive games
+        keep their visits.  A no-op for a net whose generation has not moved."""
+        self.check(L.lib.az_search_adopt_net(self._h, 1 if apply_noise else 0))
+
     @property
     def persistent(self):
         """True if the untimed simulation steps run through the persistent per-game kernel."""

@@ -240,6 +240,58 @@ __global__ void k_save_start_template(Engine E) {   // game 0's un-noised startp
     if (threadIdx.x == 0) *E.start_n = n;
 }
 
+// ------------------------------------------------------------------ adopting updated weights
+// (az_search_adopt_net / az_selfplay_adopt_net).  The live roots are rebuilt by k_root_setup from the
+// histories already in HBM; the kernels below count those rows and refresh the continuous-mode template.
+
+// the root rows just evaluated (k_root_setup's batch_count[0]) go into `evals`; the counter is cleared
+// for simulation step 0
+__global__ void k_adopt_rows_done(Engine E) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int* rows = &E.ctr->batch_count[0];
+    atomicAdd(&E.ctr->evals, (unsigned long long)load_fresh(rows));
+    *rows = 0;
+}
+
+// Where the start position is staged as a one-row batch: the last node and the last MAX_EDGES edges of
+// slot 0's arena.  A live slot was re-rooted just before (node_count == 1, edge_count <= 218), and a tree
+// of S simulations holds at most S + 1 = NMAX - 1 nodes and 218 (NMAX - 1) edges of EMAX = 218 NMAX +
+// MAX_EDGES, so neither belongs to a node of any tree, live or inactive; an expansion that ever reached
+// them would write them before anything reads them.  node_count / edge_count are not touched.
+__device__ __forceinline__ int template_node(const Engine& E) { return E.NMAX - 1; }
+__device__ __forceinline__ int template_edge0(const Engine& E) { return E.EMAX - MAX_EDGES; }
+
+__global__ void __launch_bounds__(64) k_stage_start_template(Engine E) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int g = vgpr_index(0), node = template_node(E), e0 = template_edge0(E);
+    const azc::Pos sp = azc::startpos();
+    EdgeSink sink{game_edges(E, g) + e0, 0};
+    bool chk, lep;
+    const int n = azc::gen_legal(sp, sink, &chk, &lep);
+    Node nd;
+    nd.edge_begin = (uint32_t)e0; nd.nedges = (uint16_t)n; nd.depth = 0; nd.nsum = 0; nd.parent = -1;
+    game_nodes(E, g)[node] = nd;
+    game_npos(E, g)[node] = sp;
+    E.row_game[g] = 0;                 // batch row 0 = (slot 0, the staged node)
+    E.row_node[g] = node;
+    E.ctr->batch_count[0] = 1;
+}
+
+// the evaluated, un-noised startpos edges -> start_edges / start_n (k_finish copies them into a
+// restarted slot); the row is counted and the counter cleared as in k_adopt_rows_done
+__global__ void __launch_bounds__(256) k_copy_start_template(Engine E) {
+    const int g = vgpr_index(0);
+    const Node nd = game_nodes(E, g)[template_node(E)];
+    const Edge* edges = game_edges(E, g) + nd.edge_begin;
+    for (int e = threadIdx.x; e < nd.nedges; e += blockDim.x) E.start_edges[e] = edges[e];
+    if (threadIdx.x == 0) {
+        *E.start_n = nd.nedges;
+        int* rows = &E.ctr->batch_count[0];
+        atomicAdd(&E.ctr->evals, (unsigned long long)load_fresh(rows));
+        *rows = 0;
+    }
+}
+
 // ------------------------------------------------------------------ move step
 // mode 0: self-play (choose, record, restart); mode 1: advance with given actions.
 __global__ void __launch_bounds__(64) k_finish(Engine E, int mode, const int* actions, int* results, int apply_noise) {
@@ -545,7 +597,8 @@ int adopt_net_generation(az_search* s) {
 int check_net_generation(const az_search* s, const char* who) {
     if (!s->net || s->net->dev->generation == s->net_gen) return 0;
     return fail(std::string(who) + ": the net's weights changed since this search's roots were set; set roots "
-                "(az_search_set_roots) or az_selfplay_reset first");
+                "(az_search_set_roots), az_selfplay_reset, or adopt the new weights (az_search_adopt_net / "
+                "az_selfplay_adopt_net) first");
 }
 
 constexpr int EV_PER_STEP = 9;
@@ -822,6 +875,40 @@ int setup_roots(az_search* s, int apply_noise, bool save_template) {
     k_root_noise<<<E.G, 64, 0, s->st>>>(E, apply_noise);
     AZ_HIP(hipGetLastError());
     AZ_HIP(hipStreamSynchronize(s->st));
+    return 0;
+}
+
+// az_search_adopt_net / az_selfplay_adopt_net: bring a live search over to the evaluator's current weights,
+// between moves.  Every active game's root is rebuilt from its history in HBM exactly as setup_roots builds
+// it (k_root_setup -> eval_rows -> k_root_noise: new priors, zero visits and scores, noise from the stream
+// (seed, game id, ply, 0)); history, game id, ply, slot and the host's pending records stay, inactive games
+// are not touched, the FEN cache is emptied.  Continuous mode: the start-position template is evaluated
+// again as a one-row batch of its own and copied into start_edges, so a game that starts later is played
+// wholly on the new weights.  The rows evaluated (live roots + the template) are counted in `evals`.
+int adopt_weights(az_search* s, int apply_noise, const char* who) {
+    if (!s) return fail("null search");
+    if (s->sim_cursor != 0)
+        return fail(std::string(who) + ": a move is in progress (az_selfplay_run_sims); adopt between moves");
+    if (s->cfg.evaluator == AZ_EVAL_NET && s->net->dev->generation == s->net_gen) return 0;   // nothing changed
+    AZ_HIP(hipSetDevice(s->device));
+    Engine& E = s->E;
+    if (E.cache_mask >= 0) AZ_HIP(hipMemsetAsync(E.c_state, 0, (size_t)(E.cache_mask + 1) * sizeof(unsigned), s->st));
+    AZ_HIP(hipMemsetAsync(E.ctr->batch_count, 0, sizeof(E.ctr->batch_count), s->st));
+    k_root_setup<<<(E.G + 63) / 64, 64, 0, s->st>>>(E);
+    int rc = eval_rows(s);
+    if (rc) return rc;
+    k_adopt_rows_done<<<1, 64, 0, s->st>>>(E);
+    k_root_noise<<<E.G, 64, 0, s->st>>>(E, apply_noise);
+    if (E.continuous) {
+        k_stage_start_template<<<1, 64, 0, s->st>>>(E);
+        rc = eval_rows(s);
+        if (rc) return rc;
+        k_copy_start_template<<<1, 256, 0, s->st>>>(E);
+    }
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipStreamSynchronize(s->st));
+    if (s->net) s->net_gen = s->net->dev->generation;
+    s->roots_fresh = true;
     return 0;
 }
 
@@ -1139,6 +1226,48 @@ int az_selfplay_step(az_search* s, int* finished, int* active) {
 
 int az_selfplay_run_sims(az_search* s, int nsims, int* finished, int* active, int* move_done) {
     return selfplay_sims(s, nsims, finished, active, move_done);
+}
+
+int az_selfplay_adopt_net(az_search* s) {
+    return adopt_weights(s, s ? s->cfg.noise : 0, "az_selfplay_adopt_net");
+}
+
+int az_search_adopt_net(az_search* s, int apply_noise) {
+    return adopt_weights(s, apply_noise, "az_search_adopt_net");
+}
+
+int az_selfplay_inflight(az_search* s, int32_t* game_id, int32_t* ply, int32_t* active, int32_t* moves, int32_t* off,
+                         int cap) {
+    if (!s) return fail("null search");
+    AZ_HIP(hipSetDevice(s->device));
+    AZ_HIP(hipStreamSynchronize(s->st));
+    const int G = s->E.G;
+    std::vector<int32_t> gid(G), pl(G), act(G);
+    AZ_HIP(hipMemcpy(gid.data(), s->E.game_id, (size_t)G * 4, hipMemcpyDeviceToHost));
+    AZ_HIP(hipMemcpy(pl.data(), s->E.ply, (size_t)G * 4, hipMemcpyDeviceToHost));
+    AZ_HIP(hipMemcpy(act.data(), s->E.active, (size_t)G * 4, hipMemcpyDeviceToHost));
+    // the moves so far: the steps drained from the device but not yet handed out, by game id (ply order)
+    int total = 0;
+    for (int g = 0; g < G; g++) {
+        auto it = act[g] ? s->pending.find(gid[g]) : s->pending.end();
+        total += it == s->pending.end() ? 0 : (int)it->second.size();
+    }
+    if (moves && total > cap) return fail("az_selfplay_inflight: " + std::to_string(total) + " moves, cap " + std::to_string(cap));
+    int pos = 0;
+    for (int g = 0; g < G; g++) {
+        if (game_id) game_id[g] = gid[g];
+        if (ply) ply[g] = pl[g];
+        if (active) active[g] = act[g] != 0;
+        if (off) off[g] = pos;
+        auto it = act[g] ? s->pending.find(gid[g]) : s->pending.end();
+        if (it == s->pending.end()) continue;
+        for (const StepRec& r : it->second) {
+            if (moves) moves[pos] = r.action;
+            pos++;
+        }
+    }
+    if (off) off[G] = pos;
+    return total;
 }
 
 int az_selfplay_drain(az_search* s, az_episode_step* out, int cap) {

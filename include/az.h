@@ -141,7 +141,8 @@ int az_net_forward_device(az_net* net, const float* d_planes, int n, float* d_po
  * parameters.  The work is ordered after what `stream` holds (NULL = the net's stream); the call returns
  * when the new weights are in place.  n must be the net's parameter count, else an error and no change.
  * No search may be running on the net; a search whose roots were set before the update must set roots
- * (or az_selfplay_reset) again before it runs. */
+ * (or az_selfplay_reset) again before it runs, or adopt the new weights between two moves
+ * (az_search_adopt_net / az_selfplay_adopt_net), which keeps its games. */
 int az_net_update_device(az_net* net, const float* d_weights, size_t n, void* stream);
 /* the same from host weights: one upload, then the device path (a checkpoint, an arena opponent) */
 int az_net_update(az_net* net, const float* weights, size_t n);
@@ -192,7 +193,10 @@ typedef struct {
                            order, starting at `games`.  Games that end in the same step get
                            consecutive ids in no defined slot order (it can differ from run to
                            run).  A game's content (noise, move choice: the streams keyed by
-                           seed, game id, ply) depends on its id only, never on the slot. */
+                           seed, game id, ply) depends on its id only, never on the slot.
+                           Restarted slots copy a start-position template evaluated at
+                           az_selfplay_reset; az_selfplay_adopt_net evaluates it again after a
+                           weight update. */
     int record_evals;   /* keep a log of every evaluation (for replay parity) */
     int eval_log_cap;   /* log capacity in rows */
     int cache_capacity; /* FEN evaluation cache entries (CACHE_CAPACITY, parameters.rs:4; 0 = off):
@@ -277,6 +281,34 @@ typedef struct {
     uint16_t vis_n[224];
 } az_episode_step;
 int az_selfplay_drain(az_search* s, az_episode_step* out, int cap);   /* returns count */
+
+/* Adopt the evaluator's current weights in a live search, between moves (after az_net_update* on the
+ * search's net, or when a caller-owned evaluator's model changed).  Afterwards every active game is in
+ * exactly the state az_search_set_roots would produce from that game's history on the updated evaluator
+ * (start position + the moves so far, the game's id, noise_ply = its ply, the same apply_noise): the root
+ * is evaluated again, its edges hold the new priors with zero visits and scores, and with noise on the
+ * Dirichlet noise comes from the stream (seed, game id, ply, 0) on the new priors.  The repetition
+ * history, game id, ply, slot and the steps recorded so far stay; inactive games are not touched (they keep
+ * returning the visits they had); the FEN cache is emptied.  With cfg.continuous the start-position
+ * template a restarted slot is built from is evaluated again too, so a game that starts after the call
+ * equals one played wholly on the new weights.  A game's plies before the call are the old weights', those
+ * from the call on equal a fresh search of their history on the new ones; with an evaluator that did not
+ * change the call is invisible in every result.  No history is uploaded: the state is rebuilt in HBM.
+ * AZ_EVAL_NET: 0 and no work when the net's generation has not moved since the roots were last set or
+ * adopted.  AZ_EVAL_CALLBACK / AZ_EVAL_SYNTHETIC: there is no generation, the call always re-evaluates.
+ * The rows it evaluates (one per active game, one for the template) are counted in az_search_stats.evals.
+ * Refused with an error and no change while a move is in progress (az_selfplay_run_sims).
+ * az_selfplay_adopt_net: for handles driven by az_selfplay_*, noise as cfg.noise.
+ * az_search_adopt_net: for set_roots / run / advance; the next az_search_run is valid. */
+int az_selfplay_adopt_net(az_search* s);
+int az_search_adopt_net(az_search* s, int apply_noise);
+/* The games now in the slots (logging, checkpoints): per slot the game's id, ply and active flag, read from
+ * the device, and the moves it has played so far (the recorded steps of the self-play driver) as CSR --
+ * game g's moves are moves[off[g]..off[g+1]), off has games + 1 entries; an inactive slot has none.  Any
+ * output may be NULL.  Returns the total move count; with moves == NULL that is all it needs `cap` for,
+ * otherwise an error when cap is smaller. */
+int az_selfplay_inflight(az_search* s, int32_t* game_id, int32_t* ply, int32_t* active, int32_t* moves, int32_t* off,
+                         int cap);
 
 typedef struct {
     int64_t sims;              /* simulations completed */
