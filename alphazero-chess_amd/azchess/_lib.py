@@ -44,7 +44,7 @@ class AzSearchCfg(C.Structure):
     _fields_ = [("games", C.c_int), ("sims", C.c_int), ("c_puct", C.c_float), ("dir_alpha", C.c_float),
                 ("dir_eps", C.c_float), ("temp_moves", C.c_int), ("noise", C.c_int), ("seed", C.c_uint64),
                 ("evaluator", C.c_int), ("continuous", C.c_int), ("record_evals", C.c_int),
-                ("eval_log_cap", C.c_int), ("cache_capacity", C.c_int)]
+                ("eval_log_cap", C.c_int), ("cache_capacity", C.c_int), ("leaves", C.c_int)]
 
 
 class AzEpisodeStep(C.Structure):
@@ -151,6 +151,7 @@ SIGNATURES = [
                                        P(C.c_int32), C.c_int]),
     ("az_search_stats_get", C.c_int, [C.c_void_p, P(AzSearchStats)]),
     ("az_search_persistent", C.c_int, [C.c_void_p]),
+    ("az_search_leaf_stats", C.c_int, [C.c_void_p, P(C.c_int), P(C.c_uint64)]),
     ("az_search_eval_log", C.c_int, [C.c_void_p, P(C.c_int64), P(C.c_int64), P(C.c_uint64), P(C.c_float),
                                      P(C.c_int32), P(C.c_int32), P(C.c_float)]),
     ("az_search_timing", C.c_int, [C.c_void_p, P(AzTiming), C.c_int, C.c_int]),

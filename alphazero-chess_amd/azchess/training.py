@@ -114,7 +114,8 @@ class SelfPlay:
 
 def run_all_episodes(model=None, games=100, max_moves=1000, device=0, **cfg):
     """training.rs:340-378: play `games` games from startpos to the end; returns
-    (avg_batch_size, steps) like the reference (steps of all games, game order)."""
+    (avg_batch_size, steps) like the reference (steps of all games, game order).  avg_batch_size is network
+    rows per simulation step launched; with leaves=K a step is a wave of up to K simulations per game."""
     sp = SelfPlay(model, games=games, device=device, continuous=False, **cfg)
     sp.reset()
     steps = []
@@ -125,7 +126,11 @@ def run_all_episodes(model=None, games=100, max_moves=1000, device=0, **cfg):
             break
     st = sp.search.stats()
     sims = max(st["sims"], 1)
-    avg_batch = st["evals"] / max(sims / games, 1)
+    steps_per_game = sims / games                  # simulation steps launched: with leaves=K a step is a wave
+    k, s = sp.search.leaves, sp.search.cfg.sims
+    if k > 1:
+        steps_per_game = steps_per_game * -(-s // k) / s
+    avg_batch = st["evals"] / max(steps_per_game, 1)
     return avg_batch, steps
 
 

@@ -13,10 +13,12 @@ from .parameters import CACHE_CAPACITY, C_PUCT, DIRICHLET_ALPHA, DIRICHLET_EPSIL
 
 def make_cfg(games, sims=NUM_SIMULATIONS, c_puct=C_PUCT, dir_alpha=DIRICHLET_ALPHA, dir_eps=DIRICHLET_EPSILON,
              temp_moves=TEMPERATURE_ANNEALING, noise=True, seed=SEED, synthetic=False, continuous=False,
-             record_evals=False, eval_log_cap=0, cache_capacity=CACHE_CAPACITY, callback=False):
+             record_evals=False, eval_log_cap=0, cache_capacity=CACHE_CAPACITY, callback=False, leaves=1):
+    """leaves: leaf-parallel search, K leaves per game per simulation step (1..8; 1 = the reference's
+    search).  K > 1 changes the results: see az_search_cfg.leaves."""
     kind = L.EVAL_CALLBACK if callback else (L.EVAL_SYNTHETIC if synthetic else L.EVAL_NET)
     return L.AzSearchCfg(games, sims, c_puct, dir_alpha, dir_eps, temp_moves, 1 if noise else 0, seed,
-                         kind, 1 if continuous else 0, 1 if record_evals else 0, eval_log_cap, cache_capacity)
+                         kind, 1 if continuous else 0, 1 if record_evals else 0, eval_log_cap, cache_capacity, leaves)
 
 
 def _eval_trampoline(evaluator):
@@ -128,6 +130,23 @@ class BatchedSearch:
     def persistent(self):
         """True if the untimed simulation steps run through the persistent per-game kernel."""
         return bool(L.lib.az_search_persistent(self._h))
+
+    @property
+    def leaves(self):
+        """Leaves per game per simulation step (make_cfg's `leaves`; 0 and 1 both read 1)."""
+        k = C.c_int()
+        L.check(L.lib.az_search_leaf_stats(self._h, C.byref(k), None))
+        return k.value
+
+    @property
+    def shared_leaves(self):
+        """Simulations whose leaf shared the expansion of an earlier leaf of its wave, since creation or
+        the last SelfPlay.reset() (which clears every counter of stats() too).  stats()'s sims == evals +
+        cache_hits + terminal_leaves + shared_leaves + the simulations selected onto an edge already known to
+        end the game (terminal_leaves counts an ended game once, when an expansion finds it)."""
+        n = C.c_uint64()
+        L.check(L.lib.az_search_leaf_stats(self._h, None, C.byref(n)))
+        return n.value
 
     def stats(self):
         s = L.AzSearchStats()

@@ -12,6 +12,7 @@
 
 static_assert(sizeof(az_pos) == 80, "az_pos layout");
 static_assert(sizeof(azc::Pos) == sizeof(az_pos), "Pos == az_pos");
+static_assert(sizeof(az_search_cfg) == 64, "az_search_cfg: leaves sits in the former tail padding");
 
 #ifndef AZ_WINOGRAD_DEFAULT
 #define AZ_WINOGRAD_DEFAULT 1
@@ -121,6 +122,10 @@ struct Edge {            // 16 B, one dwordx4 per lane in the select walk
 static_assert(sizeof(Node) == 16 && sizeof(Edge) == 16, "tree record layout");
 enum { CHILD_NONE = -1, CHILD_DRAW = -2, CHILD_WIN = -3 };
 enum { LEAF_EVAL = 0, LEAF_DRAW = 1, LEAF_WIN = 2, LEAF_CACHED = 3 };
+// leaf-parallel search (Engine::K > 1) only: the leaf ended on the edge an earlier new leaf of the same
+// wave (Engine::leaf_src) expands, and takes that leaf's value
+enum { LEAF_SHARED = 4 };
+constexpr int LEAVES_MAX = 8;      // az_search_cfg.leaves <= 8: one lane per earlier leaf of a wave
 constexpr int MAX_EDGES = 224;     // >= 218 legal moves
 constexpr int HMAX = 512;          // game history cap (200 fullmoves -> <= 400 plies)
 
@@ -147,6 +152,7 @@ struct Counters {                  // device-side statistics
     int log_prior_count;
     int overflow;
     int pad[1];
+    unsigned long long shared;     // shared leaves of the leaf-parallel search (az_search_leaf_stats)
 };
 
 // everything the tree kernels need, passed by value
@@ -187,6 +193,11 @@ struct Engine {
     // evaluation log
     int log_cap, log_prior_cap;
     unsigned long long* log_key; float* log_value; int* log_off; int* log_n; int* log_idx; float* log_prior;
+    // leaf-parallel search (az_search_cfg.leaves): K leaves per game per simulation step.  With K > 1 the
+    // leaf records and cached_value are [G][K], the paths [G][K][PMAX], row_game / row_node / value [G K];
+    // K = 1 is the layout above and runs the kernels above
+    int K;
+    int* leaf_src;                         // [G][K] LEAF_SHARED: the wave's leaf whose value this one takes
 };
 
 // ---------------- network ----------------

@@ -169,6 +169,46 @@ __global__ void __launch_bounds__(STEP_WPB * 64) k_step(Engine E, int step, int 
     ST_STAMP(4);
 }
 
+// ------------------------------------------------------------------ leaf-parallel steps (Engine::K > 1)
+// The same launches for a wave of k <= K leaves per game (search_dev.h select_game_k / expand_game_k /
+// backup_game_k), one wavefront = one workgroup per game.  `step` (`bstep`) is the wave's ordinal within
+// the call and names its row counter by parity; `hist` (`bhist`) its first simulation, the batch_hist entry.
+__global__ void __launch_bounds__(64) k_select_k(Engine E, int k) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= E.G || !E.active[vgpr_index(g)]) return;
+    const int ns = select_game_k(E, g, lane, k);
+    if (lane == 0 && ns) atomicAdd(&E.ctr->shared, (unsigned long long)ns);
+}
+
+__global__ void __launch_bounds__(64) k_expand_k(Engine E, int step, int k) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= E.G || !E.active[vgpr_index(g)]) return;
+    expand_game_k<1>(E, g, lane, k, step);
+}
+
+__global__ void __launch_bounds__(64) k_backup_k(Engine E, int step, int k, int hist) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g == 0 && lane == 0) backup_stats_k(E, step, hist);
+    if (g >= E.G || !E.active[vgpr_index(g)]) return;
+    backup_game_k(E, g, lane, k);
+}
+
+// k_step's sibling: backup of wave `bstep` (bk leaves; none when < 0), then select and expand of wave
+// `step` (k leaves).  The wave's backup stores, path and leaf records and tree counters are ordered
+// before its own later loads by the wavefront-scope fences inside the device functions.
+__global__ void __launch_bounds__(64) k_step_k(Engine E, int step, int k, int bstep, int bk, int bhist) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const bool live = g < E.G && E.active[vgpr_index(g)];
+    if (bstep >= 0) {
+        if (g == 0 && lane == 0) backup_stats_k(E, bstep, bhist);
+        if (live) backup_game_k(E, g, lane, bk);
+    }
+    if (!live) return;
+    const int ns = select_game_k(E, g, lane, k);
+    if (lane == 0 && ns) atomicAdd(&E.ctr->shared, (unsigned long long)ns);
+    expand_game_k<1>(E, g, lane, k, step);
+}
+
 // ------------------------------------------------------------------ roots
 // root node from hist[g][hist_len-1]; every game gets batch row g
 __global__ void __launch_bounds__(64) k_root_setup(Engine E) {
@@ -621,7 +661,7 @@ int eval_callback(az_search* s, const int* cnt) {
     int n = 0;
     AZ_HIP(hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, s->st));
     AZ_HIP(hipStreamSynchronize(s->st));
-    if (n < 0 || n > E.G) return fail("AZ_EVAL_CALLBACK: bad row count");
+    if (n < 0 || n > E.G * E.K) return fail("AZ_EVAL_CALLBACK: bad row count");
     if (n == 0) return 0;
     k_gather_rows<<<(n + 63) / 64, 64, 0, s->st>>>(E, cnt, s->d_pos);
     AZ_HIP(hipGetLastError());
@@ -640,7 +680,7 @@ int eval_callback(az_search* s, const int* cnt) {
 int eval_step(az_search* s, int step, hipEvent_t* ev) {
     Engine& E = s->E;
     hipStream_t st = s->st;
-    const int G = E.G;
+    const int G = E.G * E.K;           // the most rows a step allocates: one per leaf
     const int* cnt = &E.ctr->batch_count[step & 1];
     int rc = 0;
     if (s->cfg.evaluator == AZ_EVAL_NET) {
@@ -720,24 +760,113 @@ int eval_rows(az_search* s) {
 // k_sims32w for the untimed simulation steps: one workgroup per game, so only when the games fit
 // the chip in one round (auto), never with the FEN cache (its inserts are a separate kernel)
 bool use_persistent(const az_search* s) {
+    if (s->E.K > 1) return false;      // one leaf per step only
     if (s->persist == 0 || s->E.cache_mask >= 0 || s->cfg.evaluator != AZ_EVAL_NET) return false;
     const NetDev* n = s->net->dev;
     if (!n->fused || !sims_persistent_supported(n)) return false;
     return s->persist == 1 || s->E.G <= s->cus;
 }
 
+// the HIP events of timing mode: EV_PER_STEP per simulation
+int ensure_step_events(az_search* s) {
+    const int S = s->E.S;
+    for (int i = (int)s->ev.size(); i < EV_PER_STEP * S; i++) {
+        hipEvent_t e;
+        AZ_HIP(hipEventCreate(&e));
+        s->ev.push_back(e);
+    }
+    return 0;
+}
+
+// timing mode: the event times and row counts of the sampled steps `timed` (each the simulation index its
+// events and batch_hist entry are filed under) into s->acc
+int read_step_timing(az_search* s, const std::vector<int>& timed) {
+    const int S = s->E.S;
+    AZ_HIP(hipStreamSynchronize(s->st));
+    std::vector<int> rows(S);
+    AZ_HIP(hipMemcpy(rows.data(), s->E.batch_hist, S * 4, hipMemcpyDeviceToHost));
+    const bool net = s->cfg.evaluator == AZ_EVAL_NET;
+    const double F = net ? s->net->dev->filters : 0.0;
+    const double per_row_conv = 2.0 * 64.0 * 9.0 * F * F;
+    const double per_row_tower = net ? net_tower_flop_per_eval(s->net->dev->blocks, s->net->dev->filters) : 0.0;
+    const bool fused = net && s->net->dev->fused && tower_supported(s->net->dev);
+    for (int i : timed) {
+        hipEvent_t* e = &s->ev[EV_PER_STEP * i];
+        float t[6], tc = 0.0f;
+        for (int k = 0; k < 6; k++) (void)hipEventElapsedTime(&t[k], e[k], e[k + 1]);
+        (void)hipEventElapsedTime(&tc, e[7], e[8]);
+        az_timing& a = s->acc;
+        a.select_ms += t[0]; a.select_launches++;
+        a.expand_ms += t[1];
+        a.encode_ms += t[2];
+        a.tower_ms += t[3];
+        a.heads_ms += t[4];
+        a.backup_ms += t[5];
+        a.sim_step_ms += t[0] + t[1] + t[2] + t[3] + t[4] + t[5];
+        a.sim_steps++;
+        a.rows += rows[i];
+        if (net && rows[i] > 0 && s->net->dev->blocks > 0) {
+            a.conv_ms += tc; a.conv_launches++;
+            a.conv_flop += (fused ? per_row_tower : per_row_conv) * rows[i];
+        }
+        a.tower_flop += per_row_tower * rows[i];
+    }
+    return 0;
+}
+
+// Leaf-parallel search (cfg.leaves = K > 1): simulations [i0, i1) of the current move in waves of min(K,
+// i1 - cur) leaves per game, starting at i0 -- so how a move is cut into calls decides its waves.  A wave
+// is one simulation step: k_step_k and the evaluation of up to G K rows, its backup left to the next
+// launch; as k_select_k / k_expand_k / k_backup_k with AZ_FUSED_STEPS=0 and in the timed steps (timing
+// mode samples the waves that hold a simulation divisible by TIMING_EVERY; az_timing then counts waves).
+int run_sims_leaves(az_search* s, int i0, int i1) {
+    Engine& E = s->E;
+    hipStream_t st = s->st;
+    const int G = E.G;
+    const bool tm = s->timing;
+    if (tm && ensure_step_events(s)) return -1;
+    int pending = -1, pk = 0, ph = 0;  // ordinal, leaves and first simulation of the wave still to back up
+    std::vector<int> timed_waves;
+    int w = 0;
+    for (int i = i0; i < i1; w++) {
+        const int k = std::min(E.K, i1 - i);
+        const bool timed = tm && (i % TIMING_EVERY == 0 || i / TIMING_EVERY != (i + k - 1) / TIMING_EVERY);
+        if (timed || !s->fused_steps) {
+            hipEvent_t* ev = timed ? &s->ev[EV_PER_STEP * i] : nullptr;
+            if (pending >= 0) k_backup_k<<<G, 64, 0, st>>>(E, pending, pk, ph);
+            pending = -1;
+            if (ev) (void)hipEventRecord(ev[0], st);
+            k_select_k<<<G, 64, 0, st>>>(E, k);
+            if (ev) (void)hipEventRecord(ev[1], st);
+            k_expand_k<<<G, 64, 0, st>>>(E, w, k);
+            if (ev) (void)hipEventRecord(ev[2], st);
+            const int rc = eval_step(s, w, ev);
+            if (rc) return rc;
+            if (ev) (void)hipEventRecord(ev[5], st);
+            k_backup_k<<<G, 64, 0, st>>>(E, w, k, i);
+            if (ev) (void)hipEventRecord(ev[6], st);
+            if (timed) timed_waves.push_back(i);
+        } else {
+            k_step_k<<<G, 64, 0, st>>>(E, w, k, pending, pk, ph);
+            const int rc = eval_step(s, w, nullptr);
+            if (rc) return rc;
+            pending = w; pk = k; ph = i;
+        }
+        if (hipGetLastError() != hipSuccess) return fail("sim step launch failed");
+        i += k;
+    }
+    if (pending >= 0) k_backup_k<<<G, 64, 0, st>>>(E, pending, pk, ph);
+    AZ_HIP(hipGetLastError());
+    return tm ? read_step_timing(s, timed_waves) : 0;
+}
+
 // simulation steps [i0, i1) of the current move (run_sims(s) = the whole move)
 int run_sims(az_search* s, int i0 = 0, int i1 = -1) {
     const int S = s->E.S;
     if (i1 < 0) i1 = S;
+    if (s->E.K > 1) return run_sims_leaves(s, i0, i1);
     const bool tm = s->timing;
-    if (tm && (int)s->ev.size() < EV_PER_STEP * S) {
-        for (int i = (int)s->ev.size(); i < EV_PER_STEP * S; i++) {
-            hipEvent_t e;
-            AZ_HIP(hipEventCreate(&e));
-            s->ev.push_back(e);
-        }
-    }
+    if (tm && ensure_step_events(s)) return -1;
     // timing mode brackets every TIMING_EVERY-th simulation step with events (an event record
     // costs a few us of GPU time: on every step it was ~20 % of a 6x64 simulation step, on every
     // 8th still ~10 % of a bf16 one); those steps run as separate kernels, the others through the
@@ -782,36 +911,9 @@ int run_sims(az_search* s, int i0 = 0, int i1 = -1) {
     }
 #endif
     if (tm) {
-        AZ_HIP(hipStreamSynchronize(s->st));
-        std::vector<int> rows(S);
-        AZ_HIP(hipMemcpy(rows.data(), s->E.batch_hist, S * 4, hipMemcpyDeviceToHost));
-        const int first_timed = (i0 + TIMING_EVERY - 1) / TIMING_EVERY * TIMING_EVERY;
-        const bool net = s->cfg.evaluator == AZ_EVAL_NET;
-        const double F = net ? s->net->dev->filters : 0.0;
-        const double per_row_conv = 2.0 * 64.0 * 9.0 * F * F;
-        const double per_row_tower = net ? net_tower_flop_per_eval(s->net->dev->blocks, s->net->dev->filters) : 0.0;
-        const bool fused = net && s->net->dev->fused && tower_supported(s->net->dev);
-        for (int i = first_timed; i < i1; i += TIMING_EVERY) {
-            hipEvent_t* e = &s->ev[EV_PER_STEP * i];
-            float t[6], tc = 0.0f;
-            for (int k = 0; k < 6; k++) (void)hipEventElapsedTime(&t[k], e[k], e[k + 1]);
-            (void)hipEventElapsedTime(&tc, e[7], e[8]);
-            az_timing& a = s->acc;
-            a.select_ms += t[0]; a.select_launches++;
-            a.expand_ms += t[1];
-            a.encode_ms += t[2];
-            a.tower_ms += t[3];
-            a.heads_ms += t[4];
-            a.backup_ms += t[5];
-            a.sim_step_ms += t[0] + t[1] + t[2] + t[3] + t[4] + t[5];
-            a.sim_steps++;
-            a.rows += rows[i];
-            if (net && rows[i] > 0 && s->net->dev->blocks > 0) {
-                a.conv_ms += tc; a.conv_launches++;
-                a.conv_flop += (fused ? per_row_tower : per_row_conv) * rows[i];
-            }
-            a.tower_flop += per_row_tower * rows[i];
-        }
+        std::vector<int> timed;
+        for (int i = (i0 + TIMING_EVERY - 1) / TIMING_EVERY * TIMING_EVERY; i < i1; i += TIMING_EVERY) timed.push_back(i);
+        return read_step_timing(s, timed);
     }
     return 0;
 }
@@ -971,6 +1073,7 @@ int az_search_default_cfg(az_search_cfg* c) {
     c->record_evals = 0;
     c->eval_log_cap = 0;
     c->cache_capacity = 500000;   // CACHE_CAPACITY parameters.rs:4
+    c->leaves = 1;
     return 0;
 }
 
@@ -980,6 +1083,9 @@ int az_search_create(az_net* net, const az_search_cfg* cfg, int device, az_searc
     if (cfg->evaluator != AZ_EVAL_NET && cfg->evaluator != AZ_EVAL_SYNTHETIC && cfg->evaluator != AZ_EVAL_CALLBACK)
         return fail("bad evaluator (AZ_EVAL_NET / AZ_EVAL_SYNTHETIC / AZ_EVAL_CALLBACK)");
     if (cfg->evaluator == AZ_EVAL_NET && !net) return fail("AZ_EVAL_NET needs a network");
+    if (cfg->leaves < 0 || cfg->leaves > LEAVES_MAX)
+        return fail("bad leaves " + std::to_string(cfg->leaves) + ": leaves per game per simulation step must be in 0.." +
+                    std::to_string(LEAVES_MAX) + " (0 and 1: one leaf)");
     AZ_HIP(hipSetDevice(device));
     az_search* s = new az_search();
     s->cfg = *cfg;
@@ -992,7 +1098,9 @@ int az_search_create(az_net* net, const az_search_cfg* cfg, int device, az_searc
     AZ_HIP(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
     Engine& E = s->E;
     const int G = cfg->games, S = cfg->sims;
-    E.G = G; E.S = S; E.NMAX = S + 2; E.PMAX = S + 2;
+    const int K = std::max(cfg->leaves, 1);
+    const size_t GK = (size_t)G * K;   // leaf records and batch rows: one per game and leaf of a wave
+    E.G = G; E.S = S; E.K = K; E.NMAX = S + 2; E.PMAX = S + 2;
     E.EMAX = E.NMAX * 218 + MAX_EDGES;
     // sims <= 60000 (checked above) keeps EMAX < 2^24: child_hdr packs edge_begin in 24 bits
     E.c_puct = cfg->c_puct; E.dir_alpha = cfg->dir_alpha; E.dir_eps = cfg->dir_eps;
@@ -1003,12 +1111,13 @@ int az_search_create(az_net* net, const az_search_cfg* cfg, int device, az_searc
     rc |= dalloc(s, &E.edges, (size_t)G * E.EMAX);
     rc |= dalloc(s, &E.child_hdr, (size_t)G * E.EMAX);
     rc |= dalloc(s, &E.node_count, G); rc |= dalloc(s, &E.edge_count, G); rc |= dalloc(s, &E.max_depth, G);
-    rc |= dalloc(s, &E.leaf_node, G); rc |= dalloc(s, &E.leaf_edge, G); rc |= dalloc(s, &E.leaf_len, G);
-    rc |= dalloc(s, &E.leaf_kind, G); rc |= dalloc(s, &E.leaf_row, G);
-    rc |= dalloc(s, &E.path_node, (size_t)G * E.PMAX); rc |= dalloc(s, &E.path_edge, (size_t)G * E.PMAX);
+    rc |= dalloc(s, &E.leaf_node, GK); rc |= dalloc(s, &E.leaf_edge, GK); rc |= dalloc(s, &E.leaf_len, GK);
+    rc |= dalloc(s, &E.leaf_kind, GK); rc |= dalloc(s, &E.leaf_row, GK);
+    if (K > 1) rc |= dalloc(s, &E.leaf_src, GK);
+    rc |= dalloc(s, &E.path_node, GK * E.PMAX); rc |= dalloc(s, &E.path_edge, GK * E.PMAX);
     rc |= dalloc(s, &E.hist, (size_t)G * HMAX); rc |= dalloc(s, &E.hist_len, G);
     rc |= dalloc(s, &E.game_id, G); rc |= dalloc(s, &E.ply, G); rc |= dalloc(s, &E.active, G);
-    rc |= dalloc(s, &E.row_game, G); rc |= dalloc(s, &E.row_node, G); rc |= dalloc(s, &E.value, G);
+    rc |= dalloc(s, &E.row_game, GK); rc |= dalloc(s, &E.row_node, GK); rc |= dalloc(s, &E.value, GK);
     float* sq = nullptr;
     rc |= dalloc(s, &sq, S + 2);
     rc |= dalloc(s, &E.start_edges, MAX_EDGES); rc |= dalloc(s, &E.start_n, 1);
@@ -1016,7 +1125,7 @@ int az_search_create(az_net* net, const az_search_cfg* cfg, int device, az_searc
     rc |= dalloc(s, &E.recs, E.rec_cap);
     rc |= dalloc(s, &E.ctr, 1);
     rc |= dalloc(s, &E.batch_hist, S);
-    rc |= dalloc(s, &E.cached_value, G);
+    rc |= dalloc(s, &E.cached_value, GK);
     rc |= dalloc(s, &E.g_sims, G); rc |= dalloc(s, &E.g_sel_bytes, G); rc |= dalloc(s, &E.g_evals, G);
 #ifdef AZ_STEP_TRACE
     rc |= dalloc(s, &E.trace, (size_t)G * 16);
@@ -1048,16 +1157,16 @@ int az_search_create(az_net* net, const az_search_cfg* cfg, int device, az_searc
         if (n->device != device) { az_search_destroy(s); return fail("net and search on different devices"); }
         const size_t ab = act_bytes(n->dtype);
         char* p = nullptr;
-        rc |= dalloc(s, &p, (size_t)G * 64 * 32 * ab); s->planes = p;
-        rc |= dalloc(s, &p, (size_t)G * 64 * n->filters * ab); s->x = p;
-        rc |= dalloc(s, &p, (size_t)G * 64 * n->filters * ab); s->h = p;
+        rc |= dalloc(s, &p, GK * 64 * 32 * ab); s->planes = p;
+        rc |= dalloc(s, &p, GK * 64 * n->filters * ab); s->x = p;
+        rc |= dalloc(s, &p, GK * 64 * n->filters * ab); s->h = p;
         if (rc) { az_search_destroy(s); return -1; }
     }
     if (cfg->evaluator == AZ_EVAL_CALLBACK) {
-        rc |= dalloc(s, &s->d_pos, G); rc |= dalloc(s, &s->d_pol, (size_t)G * AZ_ACTION_SPACE); rc |= dalloc(s, &s->d_val, G);
-        if (!rc && (hipHostMalloc((void**)&s->h_pos, (size_t)G * sizeof(azc::Pos)) != hipSuccess ||
-                    hipHostMalloc((void**)&s->h_pol, (size_t)G * AZ_ACTION_SPACE * 4) != hipSuccess ||
-                    hipHostMalloc((void**)&s->h_val, (size_t)G * 4) != hipSuccess))
+        rc |= dalloc(s, &s->d_pos, GK); rc |= dalloc(s, &s->d_pol, GK * AZ_ACTION_SPACE); rc |= dalloc(s, &s->d_val, GK);
+        if (!rc && (hipHostMalloc((void**)&s->h_pos, GK * sizeof(azc::Pos)) != hipSuccess ||
+                    hipHostMalloc((void**)&s->h_pol, GK * AZ_ACTION_SPACE * 4) != hipSuccess ||
+                    hipHostMalloc((void**)&s->h_val, GK * 4) != hipSuccess))
             rc = fail("hipHostMalloc failed (evaluator staging)");
         if (rc) { az_search_destroy(s); return -1; }
     }
@@ -1283,6 +1392,19 @@ int az_selfplay_drain(az_search* s, az_episode_step* out, int cap) {
 }
 
 int az_search_persistent(az_search* s) { return s && use_persistent(s) ? 1 : 0; }
+
+int az_search_leaf_stats(az_search* s, int* leaves, uint64_t* shared_leaves) {
+    if (!s) return fail("null search");
+    if (leaves) *leaves = s->E.K;
+    if (shared_leaves) {
+        AZ_HIP(hipSetDevice(s->device));
+        AZ_HIP(hipStreamSynchronize(s->st));
+        unsigned long long sh = 0;
+        AZ_HIP(hipMemcpy(&sh, &s->E.ctr->shared, sizeof(sh), hipMemcpyDeviceToHost));
+        *shared_leaves = (uint64_t)sh;
+    }
+    return 0;
+}
 
 int az_search_stats_get(az_search* s, az_search_stats* out) {
     if (!s || !out) return fail("null argument");

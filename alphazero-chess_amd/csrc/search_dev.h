@@ -537,4 +537,298 @@ __device__ __forceinline__ void backup_game(const Engine& E, int g, int lane) {
     if (lane == 0) E.g_sims[g] += 1ull;                         // per-game slot, summed at readout
 }
 
+// ------------------------------------------------------------------ leaf-parallel search (Engine::K > 1)
+// A simulation step takes a wave of k <= K leaves per game: all k are selected on the tree
+// as it stands, leaf j seeing each earlier leaf of the wave as one more visit that lost (virtual loss, in
+// the selection arithmetic only -- nothing but backups ever writes W or N); then the new leaves are
+// expanded in order j, each a batch row of its own; the next launch backs all k up in order j.  One
+// wavefront per game, as above.  Leaf j's record is slot g K + j of the leaf arrays, its path
+// [g K + j][PMAX].  Everything below reads the per-game state through a VGPR index (vgpr_index): records
+// this wave or an earlier launch wrote with vector stores must not come back through the scalar cache.
+
+// k leaves of game g (active); returns how many of them are shared.  Lane l < j keeps leaf l's path
+// length and last edge, and at every level reads leaf l's edge of that level -- a load independent of the
+// level's edge loads, so a level stays one dependent load round.
+__device__ __forceinline__ int select_game_k(const Engine& E, int g, int lane, int k) {
+    g = vgpr_index(g);
+    const Node* nodes = game_nodes(E, g);
+    const Edge* edges = game_edges(E, g);
+    const uint32_t* chdr = E.child_hdr + (size_t)g * E.EMAX;
+    const size_t l0 = (size_t)g * E.K;
+    const float cp = E.c_puct;
+    const Node rt = nodes[0];
+    const int rbeg = __builtin_amdgcn_readfirstlane((int)rt.edge_begin);
+    const int rned = __builtin_amdgcn_readfirstlane((int)rt.nedges);
+    const int* ppe = E.path_edge + (l0 + (size_t)min(lane, k - 1)) * E.PMAX;   // lane l < j: leaf l's path
+    int my_len = 0, my_edge = -1, nshared = 0;
+    unsigned long long bytes = 0;
+    for (int j = 0; j < k; j++) {
+        int* pn = E.path_node + (l0 + j) * E.PMAX;
+        int* pe = E.path_edge + (l0 + j) * E.PMAX;
+        // lane 0's path stores of the earlier leaves before the other lanes' loads of them
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        int node = 0, len = 0, ebeg = rbeg, nedg = rned;
+        for (;;) {
+            int prev = -1;                                     // leaf `lane`'s edge at this level
+            if (lane < j && len < my_len) prev = ppe[len];
+            float best = -INFINITY;
+            int bpos = 0x7fffffff, bchild = CHILD_NONE;
+            uint32_t bhdr = 0u;
+            if (nedg <= 64) {
+                const int e = min(lane, nedg - 1);
+                const Edge ed = edges[ebeg + e];
+                const uint32_t hd = chdr[ebeg + e];
+                int c = 0;                                     // earlier leaves of the wave through this edge
+#pragma unroll
+                for (int jj = 0; jj < LEAVES_MAX - 1; jj++)
+                    if (jj < j) c += __builtin_amdgcn_readlane(prev, jj) == ebeg + e ? 1 : 0;
+                const int n = (int)ed.N + c;
+                // sum of n over the node's edges = nsum + the earlier leaves through the node
+                const int tot = wave_sum_i32(lane < nedg ? n : 0);
+                const float sq = sqrtf((float)(tot + 1));
+                const float w = ed.W - (float)c;
+                const float Nf = (float)n;
+                const float u = cp * ed.P * sq / (1.0f + Nf);
+                const float q = n > 0 ? w / Nf : 0.0f;
+                const float v = q + u;
+                if (lane < nedg && v > best) { best = v; bpos = lane; bchild = ed.child; bhdr = hd; }
+            } else {
+                const int cn = __popcll(__ballot(prev >= ebeg && prev < ebeg + nedg));
+                const int nsum = __builtin_amdgcn_readfirstlane((int)nodes[node].nsum);
+                const float sq = sqrtf((float)(nsum + cn + 1));
+                for (int e = lane; e < nedg; e += 64) {
+                    const Edge ed = edges[ebeg + e];
+                    const uint32_t hd = chdr[ebeg + e];
+                    int c = 0;
+#pragma unroll
+                    for (int jj = 0; jj < LEAVES_MAX - 1; jj++)
+                        if (jj < j) c += __builtin_amdgcn_readlane(prev, jj) == ebeg + e ? 1 : 0;
+                    const int n = (int)ed.N + c;
+                    const float w = ed.W - (float)c;
+                    const float Nf = (float)n;
+                    const float u = cp * ed.P * sq / (1.0f + Nf);
+                    const float q = n > 0 ? w / Nf : 0.0f;
+                    const float v = q + u;
+                    if (v > best) { best = v; bpos = e; bchild = ed.child; bhdr = hd; }
+                }
+            }
+            // wave argmax, first maximum in edge order (select_game)
+            int child;
+            uint32_t hdr;
+            {
+                const float wmax = wave_max_f32(best);
+                const unsigned long long hit = __ballot(best == wmax);
+                int wl;
+                if (nedg <= 64) {
+                    wl = (int)__builtin_ctzll(hit);
+                    bpos = __builtin_amdgcn_readlane(bpos, wl);
+                } else {
+                    const int mn = wave_min_i32(best == wmax ? bpos : 0x7fffffff);
+                    wl = (int)__builtin_ctzll(__ballot(best == wmax && bpos == mn));
+                    bpos = mn;
+                }
+                child = __builtin_amdgcn_readlane(bchild, wl);
+                hdr = (uint32_t)__builtin_amdgcn_readlane((int)bhdr, wl);
+            }
+            bytes += 20ull * nedg;
+            if (bpos >= nedg) {                                // every value NaN: the first edge (select_game)
+                bpos = 0;
+                child = __builtin_amdgcn_readfirstlane(edges[ebeg].child);
+                hdr = (uint32_t)__builtin_amdgcn_readfirstlane((int)chdr[ebeg]);
+            }
+            const int eabs = ebeg + bpos;
+            if (lane == 0) { pn[len] = node; pe[len] = eabs; }
+            len++;
+            if (child >= 0 && len < E.PMAX) {
+                node = child;
+                ebeg = (int)(hdr >> 8);
+                nedg = (int)(hdr & 255u);
+                continue;
+            }
+            // shared: an unexpanded edge that an earlier leaf of the wave ended on; the first of them
+            // is the new leaf that expands it
+            const unsigned long long same = __ballot(lane < j && my_edge == eabs);
+            const bool shared = child == CHILD_NONE && same != 0ull;
+            if (lane == 0) {
+                E.leaf_node[l0 + j] = node;
+                E.leaf_edge[l0 + j] = eabs;
+                E.leaf_len[l0 + j] = len;
+                E.leaf_kind[l0 + j] = child == CHILD_DRAW ? LEAF_DRAW
+                                      : child == CHILD_WIN ? LEAF_WIN : (shared ? LEAF_SHARED : LEAF_EVAL);
+                E.leaf_src[l0 + j] = shared ? (int)__builtin_ctzll(same) : -1;
+            }
+            if (lane == j) { my_len = len; my_edge = eabs; }
+            nshared += shared ? 1 : 0;
+            break;
+        }
+    }
+    if (lane == 0) E.g_sel_bytes[g] += bytes;
+    return nshared;
+}
+
+// expand_leaf_wave for leaf j of game g's wave: the same rules, cache lookup and overflow handling on the
+// leaf's own record and path.  Terminal, shared and (on an inactive game) stale leaves: X_NONE.
+template <int NW = GEN_WAVES>
+__device__ __forceinline__ int expand_leaf_k(const Engine& E, int g, int j, int lane, int* nid_out) {
+    g = vgpr_index(g);
+    // the counters and edges the wave's earlier expansions (and its selection) wrote, before they are read
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const size_t li = (size_t)g * E.K + j;
+    if (g >= E.G || !E.active[g] || E.leaf_kind[li] != LEAF_EVAL) return X_NONE;
+    Node* nodes = game_nodes(E, g);
+    Edge* edges = game_edges(E, g);
+    azc::Pos* npos = game_npos(E, g);
+    const int parent = E.leaf_node[li], eabs = E.leaf_edge[li];
+    const int idx = edges[eabs].idx & azc::IDX_MASK;
+    const azc::Pos pp = npos[parent];
+    const int ebeg = E.edge_count[g];
+    const int nid = E.node_count[g];
+    const int pdepth = nodes[parent].depth;
+    const int maxd = E.max_depth[g];
+    const int hlen = E.hist_len[g];
+    const int plen = E.leaf_len[li];
+    const int* pn = E.path_node + li * E.PMAX;
+    azc::Pos c = azc::play_index(pp, idx);
+    int n;
+    int res = leaf_rules<NW>(c, edges + ebeg, lane, &n);
+    if (res == azc::ONGOING) {                                   // repetition: the path, then the history
+        const int hm = c.halfmoves;
+        int cnt = 0;
+        for (int d0 = 2; d0 <= hm; d0 += 128) {
+            const int d = d0 + 2 * lane;
+            bool eq = false;
+            if (d <= hm) {
+                if (d <= plen) eq = azc::chess_eq(npos[pn[plen - d]], c);
+                else {
+                    const int hi = hlen - 1 - d + plen;
+                    if (hi >= 0) eq = azc::chess_eq(E.hist[(size_t)g * HMAX + hi], c);
+                }
+            }
+            cnt += __popcll(__ballot(eq));
+        }
+        if (cnt + 1 >= azc::REPETITIONS || c.halfmoves >= azc::NUM_HALFMOVES || c.fullmoves >= azc::NUM_FULLMOVES)
+            res = azc::DRAW;
+    }
+    if (res != azc::ONGOING) {
+        if (lane == 0) {
+            edges[eabs].child = res == azc::DRAW ? CHILD_DRAW : CHILD_WIN;
+            E.leaf_kind[li] = res == azc::DRAW ? LEAF_DRAW : LEAF_WIN;
+        }
+        return X_TERMINAL;
+    }
+    if (nid >= E.NMAX || ebeg + n > E.EMAX) {
+        if (lane == 0) {
+            E.leaf_kind[li] = LEAF_DRAW;
+            atomicAdd(&E.ctr->overflow, 1);
+        }
+        return X_NONE;
+    }
+    if (lane == 0) {
+        Node nn;
+        nn.edge_begin = (uint32_t)ebeg;
+        nn.nedges = (uint16_t)n;
+        nn.depth = (uint16_t)(pdepth + 1);
+        nn.nsum = 0;
+        nn.parent = parent;
+        nodes[nid] = nn;
+        npos[nid] = c;
+        E.node_count[g] = nid + 1;
+        E.edge_count[g] = ebeg + n;
+        E.child_hdr[(size_t)g * E.EMAX + eabs] = (uint32_t)ebeg << 8 | (uint32_t)n;
+        edges[eabs].child = nid;
+        if (nn.depth > maxd) E.max_depth[g] = nn.depth;
+    }
+    if (E.cache_mask >= 0) {                                     // FEN cache lookup: probe = lane
+        const uint64_t key = azc::fen_key(c);
+        bool hit = false;
+        int sl = 0;
+        if (lane < CACHE_PROBES) {
+            sl = (int)((key + (uint64_t)lane) & (uint64_t)E.cache_mask);
+            hit = E.c_state[sl] == 2u && E.c_key[sl] == key && E.c_n[sl] == n && same_fen(E.c_pos[sl], c);
+        }
+        const unsigned long long hm = __ballot(hit);
+        if (hm) {
+            const int first = __builtin_ctzll(hm);
+            sl = __shfl(sl, first, 64);
+            const float* pri = E.c_pri + (size_t)sl * MAX_EDGES;
+            for (int e = lane; e < n; e += 64) edges[ebeg + e].P = pri[e];
+            if (lane == 0) {
+                E.cached_value[li] = E.c_value[sl];
+                E.leaf_kind[li] = LEAF_CACHED;
+            }
+            return X_CACHED;
+        }
+    }
+    *nid_out = nid;
+    return X_ROW;
+}
+
+// the k expansions of game g's wave in order j, then its batch rows: one atomic per game per wave, the
+// new leaves' rows consecutive in order j (lane j keeps leaf j's outcome and node id)
+template <int NW = GEN_WAVES>
+__device__ __forceinline__ void expand_game_k(const Engine& E, int g, int lane, int k, int step) {
+    int my_kind = X_NONE, my_nid = -1;
+    for (int j = 0; j < k; j++) {
+        int nid = -1;
+        const int kind = expand_leaf_k<NW>(E, g, j, lane, &nid);
+        if (lane == j) { my_kind = kind; my_nid = nid; }
+    }
+    const unsigned long long rows = __ballot(my_kind == X_ROW);
+    const int nt = __popcll(__ballot(my_kind == X_TERMINAL)), nc = __popcll(__ballot(my_kind == X_CACHED));
+    int base = 0;
+    if (lane == 0) {
+        if (rows) base = atomicAdd(step_rows(E, step), __popcll(rows));
+        if (nt) atomicAdd(&E.ctr->terminal, (unsigned long long)nt);
+        if (nc) atomicAdd(&E.ctr->cache_hits, (unsigned long long)nc);
+    }
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (my_kind == X_ROW) {
+        const int row = base + __popcll(rows & ((1ull << lane) - 1ull));
+        E.row_game[row] = g;
+        E.row_node[row] = my_nid;
+        E.leaf_row[(size_t)g * E.K + lane] = row;
+    }
+}
+
+// backup_stats for a wave: `step` names the row counter (its parity), `hist` the batch_hist entry (the
+// wave's first simulation)
+__device__ __forceinline__ void backup_stats_k(const Engine& E, int step, int hist) {
+    int* rows = step_rows(E, step);
+    const int n = load_fresh(rows);
+    atomicAdd(&E.ctr->evals, (unsigned long long)n);
+    if (hist >= 0 && hist < E.S) E.batch_hist[hist] = n;
+    *rows = 0;
+}
+
+// the k backups of game g's wave in order j, each backup_game's update along the leaf's own path.  Lane l
+// < k reads leaf l's record and value; a shared leaf takes its source's (an earlier leaf, never itself
+// shared).  A level's edge is updated by the same lane in every backup, so the k updates of an edge that
+// several paths share are that lane's own loads and stores, in order.
+__device__ __forceinline__ void backup_game_k(const Engine& E, int g, int lane, int k) {
+    g = vgpr_index(g);
+    Node* nodes = game_nodes(E, g);
+    Edge* edges = game_edges(E, g);
+    const size_t l0 = (size_t)g * E.K;
+    const size_t ll = l0 + (size_t)min(lane, k - 1);
+    const int kind = E.leaf_kind[ll], len = E.leaf_len[ll], row = E.leaf_row[ll], src = E.leaf_src[ll];
+    const float ve = E.value[min(max(row, 0), E.G * E.K - 1)], vc = E.cached_value[ll];
+    float v = kind == LEAF_EVAL ? ve : kind == LEAF_CACHED ? vc : (kind == LEAF_DRAW ? 0.0f : -1.0f);
+    const float vs = __shfl(v, min(max(src, 0), LEAVES_MAX - 1), 64);
+    if (kind == LEAF_SHARED) v = vs;
+    for (int j = 0; j < k; j++) {
+        const float vj = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
+        const int lj = __builtin_amdgcn_readlane(len, j);
+        const int* pn = E.path_node + (l0 + j) * E.PMAX;
+        const int* pe = E.path_edge + (l0 + j) * E.PMAX;
+        for (int lv = lane; lv < lj; lv += 64) {
+            const float val = ((lj - 1 - lv) & 1) ? vj : -vj;     // value = -child value per level
+            Edge* ed = edges + pe[lv];
+            ed->W = ed->W + val;
+            ed->N = (uint16_t)(ed->N + 1);
+            nodes[pn[lv]].nsum += 1;
+        }
+    }
+    if (lane == 0) E.g_sims[g] += (unsigned long long)k;
+}
+
 }  // namespace azi

@@ -202,6 +202,16 @@ typedef struct {
     int cache_capacity; /* FEN evaluation cache entries (CACHE_CAPACITY, parameters.rs:4; 0 = off):
                            tree.rs:214-219 lookup, training.rs:413 insert.  Changes only how many
                            network rows run, never a result. */
+    int leaves;         /* leaf-parallel search: leaves per game per simulation step, K in 1..8 (0 = 1, the
+                           default: today's search, bit for bit).  With K > 1 a move's `sims` simulations run
+                           in waves of up to K per game: the K leaves of a wave are selected on the same tree,
+                           each seeing the earlier ones as visits that lost (virtual loss 1, in the selection
+                           only), expanded and evaluated in one batch of up to games * K rows, then backed
+                           up in order -- ceil(sims / K) steps a move.  A leaf that ends on the edge an
+                           earlier leaf of its wave expands shares that leaf's value (az_search_leaf_stats).
+                           Results differ from K = 1 and, with az_selfplay_run_sims, depend on how a move is
+                           cut into calls: every call starts a new wave.  Lands in the former tail padding:
+                           sizeof(az_search_cfg) stays 64. */
 } az_search_cfg;
 typedef struct az_search az_search;
 
@@ -332,6 +342,14 @@ int az_search_stats_get(az_search* s, az_search_stats* out);
  * the FEN cache is off; env AZ_PERSIST=0/1 forces it), 0 if they run as k_step + the batched
  * tower.  Either way the results are identical (tests/test_gpu_search.py). */
 int az_search_persistent(az_search* s);
+/* Leaf-parallel search: *leaves = the K in effect (1 for cfg.leaves 0 or 1), *shared_leaves = the
+ * simulations whose leaf shared the expansion of an earlier leaf of its wave (always 0 at K = 1), counted
+ * like az_search_stats: since creation or the last az_selfplay_reset, which clears every counter.  Either
+ * may be NULL.  Beside az_search_stats: sims == evals + cache_hits + terminal_leaves + shared_leaves + the
+ * simulations whose selection ended on an edge already known to end the game -- terminal_leaves counts an
+ * ended game once, when an expansion finds it, at every K; the later visits of that edge are in `sims`
+ * only.  az_search_persistent is 0 at K > 1. */
+int az_search_leaf_stats(az_search* s, int* leaves, uint64_t* shared_leaves);
 
 /* Evaluation log (cfg.record_evals): keys[n] (fen keys), values[n], CSR priors at the
  * legal move indices. Pass NULL arrays to query sizes. */
