@@ -1,24 +1,23 @@
-// arena.hip -- the evaluation arena (validation.rs:155-402) with its games in HBM (az_arena_*).
-//
-// evaluate() plays G games in lockstep, player 1 White in the even games and Black in the odd ones.
-// Here every game's positions, move list and result live on the device and az_arena_step advances
-// all live games by one ply:
-//   k_arena_stage   one wavefront per game: a base-model player's games to move are compacted into
-//                   batch rows (row = number of lower games with the same mover) and their planes are
-//                   written through plane_value (to_tensor, chess.rs:191-245); then the net's forward
-//                   (az_net_forward_device) runs on the arena's stream
-//   k_arena_pick    one wavefront per game: legal moves (gen_legal_wave), the mover's choice -- the
-//                   policy row at the legal indices under validation.rs:297-308 (last maximum, or
-//                   WeightedIndex with serial f32 sums on one lane in ascending index order), a
-//                   uniform entry of the legal-move list, or a given action -- and its validation
-//   k_arena_commit  one wavefront per game, only if every choice was valid: play_move (chess.rs:36-63)
-//                   -- play, outcome(), repetition against the game's position history, the 50-move
-//                   and 200-fullmove limits -- and the appends to the histories
-// The bodies of pick and commit are arena_dev.h's arena_pick and arena_commit, which the tournament arena
-// (tournament.hip) calls too.
-// The host keeps what the composed players need: an MCTS player's games go through the existing
-// az_search (fresh noiseless roots from a host copy of the move lists), a MiniMax player's through
-// az_minimax_scores on the downloaded positions; both come back as given actions.
+// arena.hip -- evaluation games in HBM: one lockstep match engine behind two C ABIs.
+//   az_arena_*       one match (validation.rs:155-402 evaluate): two players, or one player on both sides
+//   az_tournament_*  a round robin's pairings (ratings.rs:10-24): match m = i (i - 1) / 2 + j is
+//                    evaluate(&players[i], &players[j])
+// A match is G games, its player 1 White in the even games and Black in the odd ones.  Engine game
+// t = m * G + g is game g of match m; every game's positions, move list and result live on the device and
+// one step plays one ply of every live game of every match:
+//   k_match_stage   one wavefront per game: the games in which one player is to move, across all of its
+//                   matches, are compacted into rows 0..n-1 (ascending in t); a base-model player's rows get
+//                   their planes (plane_value: to_tensor, chess.rs:191-245) and ONE forward of n rows follows
+//                   on the engine's stream; an MCTS player's rows are the slots of its one search, whose
+//                   improved policy (search_run_device) stays in device memory
+//   k_match_pick    one wavefront per game: arena_pick (arena_dev.h) -- legal moves, the mover's choice (a
+//                   policy row under validation.rs:297-308, a uniform entry of the legal-move list, or a
+//                   given action) and its validation
+//   k_match_commit  one wavefront per game, only if every choice of every match was valid: arena_commit
+// The host keeps a mirror of results, sides to move and move lists: an MCTS player's roots are set from it
+// (az_search_set_roots_from), a MiniMax player's az_minimax_scores runs on the downloaded positions and an
+// external seat's moves are the caller's; the last two reach the kernels as given actions.
+// The engine is told which ABI it answers for, and only its messages depend on that.
 #include <string.h>
 
 #include <string>
@@ -30,95 +29,527 @@
 
 namespace azi {
 
-// device state, passed by value.  io is one block the host reads back per step:
-// [0] any bad choice, [1] live games after the ply, then status [G], chosen [G], result [G]
-struct ArenaDev {
-    int G, same, kind0, kind1, nsm;
-    azc::Pos* poshist;     // [G][HMAX]: the position after k moves at [k] (the start at [0])
-    int* moves;            // [G][HMAX]
-    int* plies;            // [G]
-    int* tomove;           // [G] player slot (0 / 1) of the mover, -1 once the game is over
-    int* row;              // [G] batch row of a base-model mover's game
-    int* io;
-    const float* u;        // [G]
-    const int* actions;    // [G]
-    const float* pol0; const float* pol1;   // [rows][4096] of the two player slots
-    __device__ __host__ int* status() const { return io + 2; }
-    __device__ __host__ int* chosen() const { return io + 2 + G; }
-    __device__ __host__ int* result() const { return io + 2 + 2 * G; }
+struct MatchPlayerDev {
+    int kind;
+    int row_base;          // the player's first row of pol
 };
 
-__global__ void __launch_bounds__(64) k_arena_reset(ArenaDev A, const azc::Pos* __restrict__ start) {
-    const int g = blockIdx.x * 64 + threadIdx.x;
-    if (g >= A.G) return;
+// device state, passed by value.  io is one block the host reads back per step:
+// [0] any bad choice, [1] live games after the ply, then status [T], chosen [T], result [T]
+struct MatchDev {
+    int T, G, nsm, pad;
+    azc::Pos* poshist;     // [T][HMAX]: the position after k moves at [k] (the start at [0])
+    int* moves;            // [T][HMAX]
+    int* plies;            // [T]
+    int* tomove;           // [T] player index of the mover, -1 once the game is over
+    int* row;              // [T] row of the game among its mover's games to move
+    int* io;
+    const int* pair;       // [matches] player 1 | player 2 << 8 (equal: one player on both sides)
+    const float* u;        // [T]
+    const int* actions;    // [T]
+    const float* pol;      // [rows][4096]: policy rows (base model) or improved-policy rows (MCTS) of all players
+    MatchPlayerDev pl[AZ_TOURNAMENT_MAX_PLAYERS];
+    __device__ __host__ int* status() const { return io + 2; }
+    __device__ __host__ int* chosen() const { return io + 2 + T; }
+    __device__ __host__ int* result() const { return io + 2 + 2 * T; }
+};
+
+// player 1 of the match is White in its even games
+__device__ __host__ __forceinline__ int match_mover(int pair, int g, int turn) {
+    return ((turn ^ g) & 1) ? (pair >> 8) : (pair & 255);
+}
+
+__global__ void __launch_bounds__(64) k_match_reset(MatchDev D, const azc::Pos* __restrict__ start) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= D.T) return;
+    const int m = t / D.G, g = t - m * D.G;
     const azc::Pos p = start[g];
-    A.poshist[(size_t)g * HMAX] = p;
-    A.plies[g] = 0;
-    A.tomove[g] = A.same ? 0 : ((p.turn ^ g) & 1);
-    A.row[g] = 0;
-    A.result()[g] = azc::ONGOING;
+    D.poshist[(size_t)t * HMAX] = p;
+    D.plies[t] = 0;
+    D.tomove[t] = match_mover(D.pair[m], g, p.turn);
+    D.row[t] = 0;
+    D.result()[t] = azc::ONGOING;
 }
 
-// current position of every game, for the host-composed players
-__global__ void __launch_bounds__(64) k_arena_positions(ArenaDev A, azc::Pos* __restrict__ out) {
-    const int g = blockIdx.x * 64 + threadIdx.x;
-    if (g >= A.G) return;
-    out[g] = A.poshist[(size_t)g * HMAX + min(A.plies[g], HMAX - 1)];
+// current position of every game, for the MiniMax players
+__global__ void __launch_bounds__(64) k_match_positions(MatchDev D, azc::Pos* __restrict__ out) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= D.T) return;
+    out[t] = D.poshist[(size_t)t * HMAX + min(D.plies[t], HMAX - 1)];
 }
 
-__global__ void __launch_bounds__(64) k_arena_stage(ArenaDev A, int slot, float* __restrict__ planes) {
-    // the per-game records were written by vector stores of earlier launches: keep g in a VGPR
-    const int g = vgpr_index(blockIdx.x), lane = threadIdx.x;
-    if (g >= A.G || A.tomove[g] != slot) return;
+// planes == nullptr (an MCTS player): the rows only
+__global__ void __launch_bounds__(64) k_match_stage(MatchDev D, int player, float* __restrict__ planes) {
+    // the per-game records were written by vector stores of earlier launches: keep t in a VGPR
+    const int t = vgpr_index(blockIdx.x), lane = threadIdx.x;
+    if (t >= D.T || D.tomove[t] != player) return;
+    // row = the lower games with the same mover; only the player's own matches can hold one (the pair
+    // table is written once, at create)
+    const int mt = t / D.G;
     int row = 0;
-    for (int j0 = 0; j0 < g; j0 += 64) {
-        const int j = j0 + lane;
-        const bool m = j < g && A.tomove[j] == slot;
-        row += __popcll(__ballot(m));
+    for (int m = 0; m <= mt; m++) {
+        const int pr = D.pair[m];
+        if ((pr & 255) != player && (pr >> 8) != player) continue;
+        const int end = m == mt ? t : (m + 1) * D.G;
+        for (int j0 = m * D.G; j0 < end; j0 += 64) {
+            const int j = j0 + lane;
+            const bool same = j < end && D.tomove[j] == player;
+            row += __popcll(__ballot(same));
+        }
     }
-    const azc::Pos p = A.poshist[(size_t)g * HMAX + A.plies[g]];
-    if (lane == 0) A.row[g] = row;
+    if (lane == 0) D.row[t] = row;
+    if (!planes) return;
+    const azc::Pos p = D.poshist[(size_t)t * HMAX + D.plies[t]];
     float* out = planes + (size_t)row * AZ_PLANES * 64;
     for (int e = lane; e < AZ_PLANES * 64; e += 64) out[e] = azc::plane_value(p, e >> 6, e & 63);
 }
 
-__global__ void __launch_bounds__(64) k_arena_pick(ArenaDev A) {
+__global__ void __launch_bounds__(64) k_match_pick(MatchDev D) {
     __shared__ PickShared S;
-    const int g = vgpr_index(blockIdx.x), lane = threadIdx.x;
-    if (g >= A.G) return;
-    const int slot = A.tomove[g];
-    if (slot < 0) return;
-    const azc::Pos p = A.poshist[(size_t)g * HMAX + A.plies[g]];
-    const int kind = slot ? A.kind1 : A.kind0;
-    const float* pol = kind == AZ_PLAYER_BASE ? (slot ? A.pol1 : A.pol0) + (size_t)A.row[g] * AZ_ACTION_SPACE : nullptr;
+    const int t = vgpr_index(blockIdx.x), lane = threadIdx.x;
+    if (t >= D.T) return;
+    const int pi = D.tomove[t];
+    if (pi < 0) return;
+    const azc::Pos p = D.poshist[(size_t)t * HMAX + D.plies[t]];
+    const MatchPlayerDev pl = D.pl[pi];
+    const float* pol = pl.kind == AZ_PLAYER_BASE || pl.kind == AZ_PLAYER_MCTS
+                           ? D.pol + ((size_t)pl.row_base + D.row[t]) * AZ_ACTION_SPACE
+                           : nullptr;
     int st;
-    const int action = arena_pick(S, p, kind, pol, A.u[g], A.actions[g], A.nsm, lane, &st);
+    const int action = arena_pick(S, p, pl.kind, pol, D.u[t], D.actions[t], D.nsm, lane, &st);
     if (lane == 0) {
-        A.chosen()[g] = action;
-        A.status()[g] = st;
-        if (st != ST_OK) atomicOr(&A.io[0], 1);
+        D.chosen()[t] = action;
+        D.status()[t] = st;
+        if (st != ST_OK) atomicOr(&D.io[0], 1);
     }
 }
 
-__global__ void __launch_bounds__(64) k_arena_commit(ArenaDev A) {
+__global__ void __launch_bounds__(64) k_match_commit(MatchDev D) {
     __shared__ Edge s_ed[MAX_EDGES];
-    const int g = vgpr_index(blockIdx.x), lane = threadIdx.x;
-    if (g >= A.G || load_fresh(&A.io[0]) != 0) return;       // all or nothing
-    if (A.tomove[g] < 0) return;
-    const int k = A.plies[g];
+    const int t = vgpr_index(blockIdx.x), lane = threadIdx.x;
+    if (t >= D.T || load_fresh(&D.io[0]) != 0) return;       // all or nothing, across every match
+    if (D.tomove[t] < 0) return;
+    const int k = D.plies[t];
     int turn;
-    const int res = arena_commit(s_ed, A.poshist + (size_t)g * HMAX, A.moves + (size_t)g * HMAX, k, A.chosen()[g], lane,
+    const int res = arena_commit(s_ed, D.poshist + (size_t)t * HMAX, D.moves + (size_t)t * HMAX, k, D.chosen()[t], lane,
                                  &turn);
     if (lane == 0) {
-        A.plies[g] = k + 1;
-        A.result()[g] = res;
-        A.tomove[g] = res != azc::ONGOING ? -1 : (A.same ? 0 : ((turn ^ g) & 1));
-        if (res == azc::ONGOING) atomicAdd(&A.io[1], 1);
+        const int m = t / D.G;
+        D.plies[t] = k + 1;
+        D.result()[t] = res;
+        D.tomove[t] = res != azc::ONGOING ? -1 : match_mover(D.pair[m], t - m * D.G, turn);
+        if (res == azc::ONGOING) atomicAdd(&D.io[1], 1);
     }
 }
 
-static int choose_host(const float* policy, int fullmoves, int nsm, float u) {
-    if (fullmoves > nsm) {                                   // Iterator::max_by: the last of equal maxima
+// which ABI a handle answers for: how its messages name the call, a player and a game
+enum Abi { ABI_ARENA, ABI_TOURNAMENT };
+
+struct MatchEngine {
+    Abi abi = ABI_ARENA;
+    int device = 0;
+    az_arena_cfg cfg{};
+    int P = 0, M = 0, G = 0, T = 0;
+    std::vector<az_arena_player> pl;
+    std::vector<int> pair;              // [M] as MatchDev::pair
+    std::vector<az_search*> search;     // [P], MCTS players only
+    std::vector<unsigned long long> evals;   // [P] the search's evaluations when it last ran
+    std::vector<int> rows_cap;          // [P] rows of the player's part of d_pol (an MCTS player's slots)
+    std::vector<float*> d_planes, d_val;
+    bool mcts_one_side = false;         // an MCTS player sits on one side of a match: reset refuses lopsided starts
+    hipStream_t st = nullptr;
+    MatchDev D{};
+    azc::Pos* d_pos = nullptr;          // [T] staging: start positions up, current positions down
+    float* d_pol = nullptr; float* d_u = nullptr; int* d_act = nullptr; int* d_pair = nullptr;
+    std::vector<void*> bufs;
+    // host mirror
+    uint64_t seed = 0;
+    std::vector<azc::Pos> start;        // [G]
+    std::vector<std::vector<int32_t>> hist;   // [T]
+    std::vector<int> result, turn;
+    std::vector<int> io;
+    std::vector<float> hu;
+    std::vector<int32_t> hact;
+    std::vector<azc::Pos> hpos;
+    double num_inferences = 0.0, rows = 0.0;
+};
+
+namespace {
+std::string fn_name(Abi abi, const char* call) {
+    return std::string(abi == ABI_ARENA ? "az_arena_" : "az_tournament_") + call + ": ";
+}
+
+// the arena's players are 1 and 2, a tournament's count from 0
+std::string player_name(Abi abi, int i) { return "player " + std::to_string(abi == ABI_ARENA ? i + 1 : i); }
+
+std::string game_name(const MatchEngine* e, int t) {
+    const std::string game = "game " + std::to_string(t % e->G);
+    return e->abi == ABI_ARENA ? game : "match " + std::to_string(t / e->G) + " " + game;
+}
+
+int player_ok(Abi abi, const az_arena_player* p, int i) {
+    const std::string fn = fn_name(abi, "create"), which = player_name(abi, i);
+    if (!p) return fail(fn + "null " + which);
+    if (p->kind == AZ_PLAYER_EXTERNAL && abi == ABI_TOURNAMENT)
+        return fail(fn + which + " is external; a tournament has no such seat");
+    if (p->kind < AZ_PLAYER_MCTS || p->kind > AZ_PLAYER_EXTERNAL) return fail(fn + "bad kind of " + which);
+    if (p->kind == AZ_PLAYER_BASE && !p->net) return fail(fn + which + " is a base-model player without a net");
+    if (p->kind == AZ_PLAYER_MINIMAX && (p->depth < 1 || p->depth > AZ_MINIMAX_MAX_DEPTH))
+        return fail(fn + "MiniMax depth of " + which + " outside 1.." + std::to_string(AZ_MINIMAX_MAX_DEPTH));
+    if ((p->kind == AZ_PLAYER_BASE || p->kind == AZ_PLAYER_MCTS) && p->net && !p->net->dev)
+        return fail(fn + which + " has a dead net");
+    return 0;
+}
+
+template <class T> int dmalloc(MatchEngine* e, T** p, size_t count) {
+    void* q = nullptr;
+    const size_t bytes = count * sizeof(T);
+    AZ_HIP(hipMalloc(&q, bytes < 16 ? 16 : bytes));
+    e->bufs.push_back(q);
+    *p = (T*)q;
+    return 0;
+}
+}  // namespace
+
+int match_destroy(MatchEngine* e) {
+    if (!e) return 0;
+    (void)hipSetDevice(e->device);
+    if (e->st) (void)hipStreamSynchronize(e->st);
+    for (az_search* s : e->search) if (s) az_search_destroy(s);
+    for (void* p : e->bufs) (void)hipFree(p);
+    if (e->st) (void)hipStreamDestroy(e->st);
+    delete e;
+    return 0;
+}
+
+int match_reset(MatchEngine* e, const az_pos* start, uint64_t seed) {
+    const std::string fn = fn_name(e->abi, "reset");
+    const int G = e->G, T = e->T;
+    std::vector<azc::Pos> sp(G, azc::startpos());
+    for (int g = 0; start && g < G; g++) {
+        azc::Pos p = *reinterpret_cast<const azc::Pos*>(start + g);
+        if (const char* why = azc::setup_error(p))
+            return fail(fn + "start position of game " + std::to_string(g) + " rejected: " + why);
+        bool chk;
+        const int n = azc::finalize(p, &chk);
+        if (azc::outcome(p, n, chk) != azc::ONGOING)
+            return fail(fn + "start position of game " + std::to_string(g) + " is already decided");
+        sp[g] = p;
+    }
+    // in every match player 1 moves in `first` games on the even plies and player 2 in the others: an MCTS
+    // player's search holds (games + 1) / 2 roots per match unless it plays both sides
+    int first = 0;
+    for (int g = 0; g < G; g++) first += ((sp[g].turn ^ g) & 1) == 0;
+    const int half = (G + 1) / 2;
+    if (e->mcts_one_side && (first > half || G - first > half)) {
+        const bool arena = e->abi == ABI_ARENA;
+        return fail(fn + "with these start positions one player is to move in " +
+                    std::to_string(first > G - first ? first : G - first) + " games" + (arena ? "" : " of a match") +
+                    " at once; an MCTS player's search holds " + std::to_string(half) + (arena ? "" : " per match"));
+    }
+    AZ_HIP(hipSetDevice(e->device));
+    for (int i = 0; i < e->P; i++) {
+        if (!e->search[i]) continue;
+        az_search_stats s0;
+        if (az_search_stats_get(e->search[i], &s0)) return -1;
+        e->evals[i] = (unsigned long long)s0.evals;
+    }
+    AZ_HIP(hipMemcpyAsync(e->d_pos, sp.data(), (size_t)G * sizeof(azc::Pos), hipMemcpyHostToDevice, e->st));
+    k_match_reset<<<(T + 63) / 64, 64, 0, e->st>>>(e->D, e->d_pos);
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipStreamSynchronize(e->st));
+    e->seed = seed;
+    e->start = sp;
+    e->hist.assign(T, std::vector<int32_t>());
+    e->result.assign(T, azc::ONGOING);
+    e->turn.resize(T);
+    for (int t = 0; t < T; t++) e->turn[t] = sp[t % G].turn;
+    e->num_inferences = e->rows = 0.0;
+    return 0;
+}
+
+// players [P] (checked here, before the first device call); pair [M] as MatchDev::pair
+int match_create(Abi abi, const az_arena_player* const* players, int P, const std::vector<int>& pair,
+                 const az_arena_cfg* cfg, int device, MatchEngine** out) {
+    const std::string fn = fn_name(abi, "create");
+    bool mcts = false;
+    for (int i = 0; i < P; i++) {
+        if (player_ok(abi, players[i], i)) return -1;
+        mcts |= players[i]->kind == AZ_PLAYER_MCTS;
+    }
+    if (cfg->games <= 0) return fail(fn + "games must be positive");
+    if (mcts && cfg->sims <= 0) return fail(fn + "an MCTS player needs sims > 0");
+    for (int i = 0; i < P; i++) {
+        const az_arena_player& p = *players[i];
+        if (p.net && (p.kind == AZ_PLAYER_BASE || p.kind == AZ_PLAYER_MCTS) && p.net->dev->device != device)
+            return fail(fn + (abi == ABI_ARENA ? "a player's net" : "the net of " + player_name(abi, i)) +
+                        " is on another device");
+    }
+    AZ_HIP(hipSetDevice(device));
+    MatchEngine* e = new MatchEngine();
+    e->abi = abi;
+    e->device = device;
+    e->cfg = *cfg;
+    e->P = P;
+    const int M = e->M = (int)pair.size();
+    const int G = e->G = cfg->games;
+    const int T = e->T = M * G;
+    for (int i = 0; i < P; i++) e->pl.push_back(*players[i]);
+    e->pair = pair;
+    e->search.assign(P, nullptr);
+    e->evals.assign(P, 0ull);
+    e->rows_cap.assign(P, 0);
+    e->d_planes.assign(P, nullptr);
+    e->d_val.assign(P, nullptr);
+    // per match, with caller-given start positions a base-model player can be to move in all G games; an
+    // MCTS player's search holds (G + 1) / 2 roots (match_reset refuses more), G when it plays both sides
+    for (int pr : pair) {
+        const bool both = (pr & 255) == (pr >> 8);
+        for (int side = 0; side < (both ? 1 : 2); side++) {
+            const int i = side ? pr >> 8 : pr & 255;
+            const int k = e->pl[i].kind;
+            e->rows_cap[i] += k == AZ_PLAYER_BASE ? G : k == AZ_PLAYER_MCTS ? (both ? G : (G + 1) / 2) : 0;
+            e->mcts_one_side |= k == AZ_PLAYER_MCTS && !both;
+        }
+    }
+    auto build = [&]() -> int {
+        AZ_HIP(hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking));
+        MatchDev& D = e->D;
+        D.T = T;
+        D.G = G;
+        D.nsm = cfg->num_stochastic_moves;
+        if (dmalloc(e, &D.poshist, (size_t)T * HMAX) || dmalloc(e, &D.moves, (size_t)T * HMAX) || dmalloc(e, &D.plies, T) ||
+            dmalloc(e, &D.tomove, T) || dmalloc(e, &D.row, T) || dmalloc(e, &D.io, 2 + 3 * (size_t)T) ||
+            dmalloc(e, &e->d_pos, T) || dmalloc(e, &e->d_u, T) || dmalloc(e, &e->d_act, T) || dmalloc(e, &e->d_pair, M))
+            return -1;
+        AZ_HIP(hipMemsetAsync(e->d_act, 0xff, (size_t)T * 4, e->st));
+        AZ_HIP(hipMemcpy(e->d_pair, pair.data(), (size_t)M * 4, hipMemcpyHostToDevice));
+        D.pair = e->d_pair;
+        D.u = e->d_u;
+        D.actions = e->d_act;
+        size_t total = 0;
+        for (int i = 0; i < P; i++) {
+            D.pl[i].kind = e->pl[i].kind;
+            D.pl[i].row_base = (int)total;
+            total += (size_t)e->rows_cap[i];
+        }
+        if (total > 0x7fffffffull) return fail(fn + "too many policy rows");
+        if (dmalloc(e, &e->d_pol, total * AZ_ACTION_SPACE)) return -1;
+        D.pol = e->d_pol;
+        for (int i = 0; i < P; i++) {
+            const az_arena_player& p = e->pl[i];
+            if (p.kind == AZ_PLAYER_BASE) {
+                if (dmalloc(e, &e->d_planes[i], (size_t)e->rows_cap[i] * AZ_PLANES * 64) ||
+                    dmalloc(e, &e->d_val[i], (size_t)e->rows_cap[i]))
+                    return -1;
+            } else if (p.kind == AZ_PLAYER_MCTS) {
+                az_search_cfg sc;
+                az_search_default_cfg(&sc);
+                sc.games = e->rows_cap[i];
+                sc.sims = cfg->sims;
+                sc.c_puct = cfg->c_puct;
+                sc.noise = 0;
+                sc.seed = cfg->seed;
+                sc.evaluator = p.net ? AZ_EVAL_NET : AZ_EVAL_SYNTHETIC;
+                sc.continuous = 0;
+                sc.record_evals = 0;
+                sc.eval_log_cap = 0;
+                sc.cache_capacity = 0;
+                if (az_search_create(p.net, &sc, device, &e->search[i])) return -1;
+            }
+        }
+        e->io.resize(2 + 3 * (size_t)T);
+        return 0;
+    };
+    if (build() || match_reset(e, nullptr, cfg->seed)) {
+        const std::string why = az_last_error();
+        match_destroy(e);
+        return fail(why);
+    }
+    *out = e;
+    return 0;
+}
+
+// one ply of every live game of every match; actions [T] (may be nullptr): the external seats' moves
+int match_step(MatchEngine* e, const float* u, const int32_t* actions, int* live) {
+    const std::string fn = fn_name(e->abi, "step");
+    const int G = e->G, T = e->T, P = e->P;
+    MatchDev& D = e->D;
+    AZ_HIP(hipSetDevice(e->device));
+    // this ply's movers per player, ascending in t, from the host mirror
+    std::vector<std::vector<int>> mv(P);
+    int nlive = 0;
+    for (int t = 0; t < T; t++)
+        if (e->result[t] == azc::ONGOING) { mv[match_mover(e->pair[t / G], t % G, e->turn[t])].push_back(t); nlive++; }
+    if (nlive == 0) {
+        if (live) *live = 0;
+        return 0;
+    }
+    std::vector<float>& hu = e->hu;
+    hu.assign(T, 0.0f);
+    for (int t = 0; t < T; t++) {
+        if (u) { hu[t] = u[t]; continue; }
+        uint64_t ctr = 0;
+        hu[t] = azc::uniform01(azc::stream_key(e->seed, (uint64_t)(t % G), (uint64_t)e->hist[t].size(), 2), ctr);
+    }
+    double ninf = 0.0, nrows = 0.0;
+    AZ_HIP(hipMemsetAsync(D.io, 0, (2 + 2 * (size_t)T) * 4, e->st));
+    AZ_HIP(hipMemcpyAsync(e->d_u, hu.data(), (size_t)T * 4, hipMemcpyHostToDevice, e->st));
+    std::vector<int32_t>& hact = e->hact;
+    hact.assign(T, -1);
+    bool given = false, positions = false;
+    for (int i = 0; i < P; i++) {
+        if (mv[i].empty()) continue;
+        const az_arena_player& p = e->pl[i];
+        if (p.kind == AZ_PLAYER_EXTERNAL) {
+            if (!actions) return fail(fn + game_name(e, mv[i][0]) + " has an external mover and actions is NULL");
+            for (int t : mv[i]) hact[t] = actions[t];
+            given = true;
+        } else if (p.kind == AZ_PLAYER_MINIMAX) {
+            if (!positions) {                                // one download serves every MiniMax player
+                k_match_positions<<<(T + 63) / 64, 64, 0, e->st>>>(D, e->d_pos);
+                AZ_HIP(hipGetLastError());
+                e->hpos.resize(T);
+                AZ_HIP(hipMemcpyAsync(e->hpos.data(), e->d_pos, (size_t)T * sizeof(azc::Pos), hipMemcpyDeviceToHost, e->st));
+                AZ_HIP(hipStreamSynchronize(e->st));
+                positions = true;
+            }
+            const int n = (int)mv[i].size();
+            std::vector<azc::Pos> pos(n);
+            for (int k = 0; k < n; k++) pos[k] = e->hpos[mv[i][k]];
+            std::vector<int32_t> m((size_t)n * AZ_MAX_MOVES), pr((size_t)n * AZ_MAX_MOVES), sc((size_t)n * AZ_MAX_MOVES), nm(n);
+            if (az_minimax_scores(e->device, reinterpret_cast<const az_pos*>(pos.data()), n, p.depth, m.data(), pr.data(),
+                                  sc.data(), nm.data(), nullptr))
+                return -1;
+            for (int k = 0; k < n; k++) {
+                const int t = mv[i][k];
+                const int b = az_minimax_best(sc.data() + (size_t)k * AZ_MAX_MOVES, nm[k], hu[t]);
+                hact[t] = b >= 0 ? m[(size_t)k * AZ_MAX_MOVES + b] : -1;
+            }
+            AZ_HIP(hipSetDevice(e->device));
+            given = true;
+        } else if (p.kind == AZ_PLAYER_MCTS) {
+            // a fresh noiseless tree per move (MCTree::async_init(.., false)) through the set-roots path,
+            // from the host copy of the move lists; spare slots repeat the player's first root
+            az_search* s = e->search[i];
+            const int S = e->rows_cap[i], n = (int)mv[i].size();
+            if (n > S) return fail(fn + "more games to move than the MCTS player's search holds");
+            std::vector<azc::Pos> st(S);
+            std::vector<int32_t> flat, off(S + 1, 0), gid(S), nply(S);
+            for (int k = 0; k < S; k++) {
+                const int t = mv[i][k < n ? k : 0];
+                st[k] = e->start[t % G];
+                flat.insert(flat.end(), e->hist[t].begin(), e->hist[t].end());
+                off[k + 1] = (int32_t)flat.size();
+                gid[k] = k;
+                nply[k] = (int32_t)e->hist[t].size();
+            }
+            flat.push_back(0);
+            if (az_search_set_roots_from(s, reinterpret_cast<const az_pos*>(st.data()), flat.data(), off.data(), gid.data(),
+                                         nply.data(), 0))
+                return -1;
+            unsigned long long ev = 0;
+            if (search_run_device(s, e->d_pol + (size_t)D.pl[i].row_base * AZ_ACTION_SPACE, &ev)) return -1;
+            AZ_HIP(hipSetDevice(e->device));
+            ninf += (double)e->cfg.sims + 1.0;
+            nrows += (double)(ev - e->evals[i]);
+            e->evals[i] = ev;
+            k_match_stage<<<T, 64, 0, e->st>>>(D, i, nullptr);   // the games' slot rows
+            AZ_HIP(hipGetLastError());
+        }
+    }
+    // one stage launch and one forward per base-model player, over its games to move in all its matches
+    for (int i = 0; i < P; i++) {
+        if (mv[i].empty() || e->pl[i].kind != AZ_PLAYER_BASE) continue;
+        const int n = (int)mv[i].size();
+        if (n > e->rows_cap[i]) return fail(fn + "more games to move than a base player's batch holds");
+        k_match_stage<<<T, 64, 0, e->st>>>(D, i, e->d_planes[i]);
+        AZ_HIP(hipGetLastError());
+        if (az_net_forward_device(e->pl[i].net, e->d_planes[i], n, e->d_pol + (size_t)D.pl[i].row_base * AZ_ACTION_SPACE,
+                                  e->d_val[i], e->st))
+            return -1;
+        AZ_HIP(hipSetDevice(e->device));
+        ninf += 1.0;
+        nrows += (double)n;
+    }
+    if (given) AZ_HIP(hipMemcpyAsync(e->d_act, hact.data(), (size_t)T * 4, hipMemcpyHostToDevice, e->st));
+    k_match_pick<<<T, 64, 0, e->st>>>(D);
+    AZ_HIP(hipGetLastError());
+    k_match_commit<<<T, 64, 0, e->st>>>(D);
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipMemcpyAsync(e->io.data(), D.io, e->io.size() * 4, hipMemcpyDeviceToHost, e->st));
+    AZ_HIP(hipStreamSynchronize(e->st));
+    const int* status = e->io.data() + 2;
+    const int* chosen = e->io.data() + 2 + T;
+    const int* result = e->io.data() + 2 + 2 * T;
+    if (e->io[0]) {                                          // nothing was committed, in any match
+        for (int t = 0; t < T; t++) {
+            if (status[t] == ST_NONFINITE) return fail(fn + game_name(e, t) + ": the policy has a non-finite legal entry");
+            if (status[t] == ST_ILLEGAL)
+                return fail(fn + game_name(e, t) + ": index " + std::to_string(chosen[t]) + " is not a legal move");
+        }
+        return fail(fn + "a move was refused");
+    }
+    for (int i = 0; i < P; i++)
+        for (int t : mv[i]) {
+            e->hist[t].push_back(chosen[t]);
+            e->turn[t] ^= 1;
+            e->result[t] = result[t];
+        }
+    e->num_inferences += ninf;
+    e->rows += nrows;
+    if (live) *live = e->io[1];
+    return 0;
+}
+
+int match_results(MatchEngine* e, int32_t* result, int32_t* plies) {
+    AZ_HIP(hipSetDevice(e->device));
+    if (result) AZ_HIP(hipMemcpyAsync(result, e->D.result(), (size_t)e->T * 4, hipMemcpyDeviceToHost, e->st));
+    if (plies) AZ_HIP(hipMemcpyAsync(plies, e->D.plies, (size_t)e->T * 4, hipMemcpyDeviceToHost, e->st));
+    AZ_HIP(hipStreamSynchronize(e->st));
+    return 0;
+}
+
+// from the host mirror: no device access
+int match_live(MatchEngine* e, int32_t* live) {
+    int n = 0;
+    for (int t = 0; t < e->T; t++) n += live[t] = e->result[t] == azc::ONGOING ? 1 : 0;
+    return n;
+}
+
+int match_history(MatchEngine* e, int t, int32_t* moves, int cap) {
+    AZ_HIP(hipSetDevice(e->device));
+    int n = 0;
+    AZ_HIP(hipMemcpyAsync(&n, e->D.plies + t, 4, hipMemcpyDeviceToHost, e->st));
+    AZ_HIP(hipStreamSynchronize(e->st));
+    const int m = n < cap ? n : cap;
+    if (moves && m > 0) {
+        AZ_HIP(hipMemcpyAsync(moves, e->D.moves + (size_t)t * HMAX, (size_t)m * 4, hipMemcpyDeviceToHost, e->st));
+        AZ_HIP(hipStreamSynchronize(e->st));
+    }
+    return n;
+}
+
+int match_stats(MatchEngine* e, double* num_inferences, double* rows) {
+    if (num_inferences) *num_inferences = e->num_inferences;
+    if (rows) *rows = e->rows;
+    return 0;
+}
+
+}  // namespace azi
+
+using namespace azi;
+
+// az_arena and az_tournament are the C names of a MatchEngine
+static MatchEngine* engine(az_arena* a) { return reinterpret_cast<MatchEngine*>(a); }
+static MatchEngine* engine(az_tournament* t) { return reinterpret_cast<MatchEngine*>(t); }
+
+extern "C" {
+
+// ---------------------------------------------------------------- az_arena_*: one match
+int az_arena_choose(const float* policy, int fullmoves, int num_stochastic_moves, float u) {
+    if (!policy) return fail("az_arena_choose: null policy");
+    if (fullmoves > num_stochastic_moves) {                  // Iterator::max_by: the last of equal maxima
         int best = 0;
         for (int i = 1; i < AZ_ACTION_SPACE; i++) if (!(policy[i] < policy[best])) best = i;
         return best;
@@ -135,358 +566,121 @@ static int choose_host(const float* policy, int fullmoves, int nsm, float u) {
     return AZ_ACTION_SPACE - 1;
 }
 
-}  // namespace azi
-
-using namespace azi;
-
-struct az_arena {
-    int device = 0;
-    az_arena_cfg cfg{};
-    az_arena_player pl[2]{};
-    bool same = false;
-    az_search* search[2] = {nullptr, nullptr};
-    int slots = 0;
-    hipStream_t st = nullptr;
-    ArenaDev A{};
-    azc::Pos* d_pos = nullptr;          // [G] staging: start positions up, current positions down
-    float* d_u = nullptr; int* d_act = nullptr;
-    float* d_planes[2] = {nullptr, nullptr}; float* d_pol[2] = {nullptr, nullptr}; float* d_val[2] = {nullptr, nullptr};
-    std::vector<void*> bufs;
-    // host mirror (what the composed players and the bookkeeping need)
-    uint64_t seed = 0;
-    std::vector<azc::Pos> start;
-    std::vector<std::vector<int32_t>> hist;
-    std::vector<int> result, turn, fullmoves;
-    std::vector<int> io;
-    std::vector<float> improved, hu;
-    std::vector<int32_t> hact;
-    double num_inferences = 0.0, rows = 0.0;
-};
-
-namespace {
-int player_ok(const az_arena_player* p, const char* which) {
-    if (!p) return fail(std::string("az_arena_create: null ") + which);
-    if (p->kind < AZ_PLAYER_MCTS || p->kind > AZ_PLAYER_EXTERNAL) return fail(std::string("az_arena_create: bad kind of ") + which);
-    if (p->kind == AZ_PLAYER_BASE && !p->net) return fail(std::string("az_arena_create: ") + which + " is a base-model player without a net");
-    if (p->kind == AZ_PLAYER_MINIMAX && (p->depth < 1 || p->depth > AZ_MINIMAX_MAX_DEPTH))
-        return fail(std::string("az_arena_create: MiniMax depth of ") + which + " outside 1.." + std::to_string(AZ_MINIMAX_MAX_DEPTH));
-    if ((p->kind == AZ_PLAYER_BASE || p->kind == AZ_PLAYER_MCTS) && p->net && !p->net->dev)
-        return fail(std::string("az_arena_create: ") + which + " has a dead net");
-    return 0;
-}
-
-template <class T> int dmalloc(az_arena* a, T** p, size_t count) {
-    void* q = nullptr;
-    const size_t bytes = count * sizeof(T);
-    AZ_HIP(hipMalloc(&q, bytes < 16 ? 16 : bytes));
-    a->bufs.push_back(q);
-    *p = (T*)q;
-    return 0;
-}
-
-inline int slot_of(const az_arena* a, int g) { return a->same ? 0 : ((a->turn[g] ^ g) & 1); }
-}  // namespace
-
-extern "C" {
-
-int az_arena_choose(const float* policy, int fullmoves, int num_stochastic_moves, float u) {
-    if (!policy) return fail("az_arena_choose: null policy");
-    return choose_host(policy, fullmoves, num_stochastic_moves, u);
-}
-
-int az_arena_destroy(az_arena* a) {
-    if (!a) return 0;
-    (void)hipSetDevice(a->device);
-    if (a->st) (void)hipStreamSynchronize(a->st);
-    for (int k = 0; k < 2; k++) if (a->search[k]) az_search_destroy(a->search[k]);
-    for (void* p : a->bufs) (void)hipFree(p);
-    if (a->st) (void)hipStreamDestroy(a->st);
-    delete a;
-    return 0;
-}
-
 int az_arena_create(const az_arena_player* p1, const az_arena_player* p2, const az_arena_cfg* cfg, int device,
                     az_arena** out) {
     if (!cfg || !out) return fail("az_arena_create: null argument");
-    if (player_ok(p1, "player 1") || player_ok(p2, "player 2")) return -1;
-    if (cfg->games <= 0) return fail("az_arena_create: games must be positive");
-    const bool mcts = p1->kind == AZ_PLAYER_MCTS || p2->kind == AZ_PLAYER_MCTS;
-    if (mcts && cfg->sims <= 0) return fail("az_arena_create: an MCTS player needs sims > 0");
-    for (const az_arena_player* p : {p1, p2})
-        if (p->net && (p->kind == AZ_PLAYER_BASE || p->kind == AZ_PLAYER_MCTS) && p->net->dev->device != device)
-            return fail("az_arena_create: a player's net is on another device");
-    AZ_HIP(hipSetDevice(device));
-    az_arena* a = new az_arena();
-    a->device = device;
-    a->cfg = *cfg;
-    a->pl[0] = *p1;
-    a->pl[1] = *p2;
-    a->same = p1 == p2;
-    const int G = cfg->games;
-    a->slots = a->same ? G : (G + 1) / 2;
-    auto build = [&]() -> int {
-        AZ_HIP(hipStreamCreateWithFlags(&a->st, hipStreamNonBlocking));
-        ArenaDev& A = a->A;
-        A.G = G;
-        A.same = a->same ? 1 : 0;
-        A.kind0 = p1->kind;
-        A.kind1 = p2->kind;
-        A.nsm = cfg->num_stochastic_moves;
-        if (dmalloc(a, &A.poshist, (size_t)G * HMAX) || dmalloc(a, &A.moves, (size_t)G * HMAX) || dmalloc(a, &A.plies, G) ||
-            dmalloc(a, &A.tomove, G) || dmalloc(a, &A.row, G) || dmalloc(a, &A.io, 2 + 3 * (size_t)G) ||
-            dmalloc(a, &a->d_pos, G) || dmalloc(a, &a->d_u, G) || dmalloc(a, &a->d_act, G))
-            return -1;
-        A.u = a->d_u;
-        A.actions = a->d_act;
-        for (int k = 0; k < (a->same ? 1 : 2); k++) {
-            const az_arena_player& p = a->pl[k];
-            if (p.kind == AZ_PLAYER_BASE) {
-                // with caller-given start positions one player can be to move in every game
-                if (dmalloc(a, &a->d_planes[k], (size_t)G * AZ_PLANES * 64) ||
-                    dmalloc(a, &a->d_pol[k], (size_t)G * AZ_ACTION_SPACE) || dmalloc(a, &a->d_val[k], G))
-                    return -1;
-            } else if (p.kind == AZ_PLAYER_MCTS) {
-                az_search_cfg sc;
-                az_search_default_cfg(&sc);
-                sc.games = a->slots;
-                sc.sims = cfg->sims;
-                sc.c_puct = cfg->c_puct;
-                sc.noise = 0;
-                sc.seed = cfg->seed;
-                sc.evaluator = p.net ? AZ_EVAL_NET : AZ_EVAL_SYNTHETIC;
-                sc.continuous = 0;
-                sc.record_evals = 0;
-                sc.eval_log_cap = 0;
-                sc.cache_capacity = 0;
-                if (az_search_create(p.net, &sc, device, &a->search[k])) return -1;
-            }
-        }
-        A.pol0 = a->d_pol[0];
-        A.pol1 = a->same ? a->d_pol[0] : a->d_pol[1];
-        a->improved.resize(mcts ? (size_t)a->slots * AZ_ACTION_SPACE : 0);
-        a->io.resize(2 + 3 * (size_t)G);
-        return 0;
-    };
-    if (build() || az_arena_reset(a, nullptr, cfg->seed)) {
-        const std::string why = az_last_error();
-        az_arena_destroy(a);
-        return fail(why);
-    }
-    *out = a;
+    const az_arena_player* players[2] = {p1, p2};
+    const bool same = p1 && p1 == p2;                        // one player on both sides: pair (0, 0), else (0, 1)
+    MatchEngine* e = nullptr;
+    if (match_create(ABI_ARENA, players, same ? 1 : 2, {same ? 0 : 1 << 8}, cfg, device, &e)) return -1;
+    *out = reinterpret_cast<az_arena*>(e);
     return 0;
 }
 
+int az_arena_destroy(az_arena* a) { return match_destroy(engine(a)); }
+
 int az_arena_reset(az_arena* a, const az_pos* start, uint64_t seed) {
     if (!a) return fail("az_arena_reset: null arena");
-    const int G = a->A.G;
-    std::vector<azc::Pos> sp(G, azc::startpos());
-    for (int g = 0; start && g < G; g++) {
-        azc::Pos p = *reinterpret_cast<const azc::Pos*>(start + g);
-        if (const char* why = azc::setup_error(p))
-            return fail("az_arena_reset: start position of game " + std::to_string(g) + " rejected: " + why);
-        bool chk;
-        const int n = azc::finalize(p, &chk);
-        if (azc::outcome(p, n, chk) != azc::ONGOING)
-            return fail("az_arena_reset: start position of game " + std::to_string(g) + " is already decided");
-        sp[g] = p;
-    }
-    // player 1 moves in `first` games on the even plies and in the others on the odd ones, player 2 the
-    // other way round: an MCTS player's search holds (games + 1) / 2 roots unless it plays both sides
-    int first = 0;
-    for (int g = 0; g < G; g++) first += ((sp[g].turn ^ g) & 1) == 0;
-    const bool mcts = a->pl[0].kind == AZ_PLAYER_MCTS || a->pl[1].kind == AZ_PLAYER_MCTS;
-    if (mcts && !a->same && (first > a->slots || G - first > a->slots))
-        return fail("az_arena_reset: with these start positions one player is to move in " +
-                    std::to_string(first > G - first ? first : G - first) + " games at once; an MCTS player's search holds " +
-                    std::to_string(a->slots));
-    AZ_HIP(hipSetDevice(a->device));
-    AZ_HIP(hipMemcpyAsync(a->d_pos, sp.data(), (size_t)G * sizeof(azc::Pos), hipMemcpyHostToDevice, a->st));
-    k_arena_reset<<<(G + 63) / 64, 64, 0, a->st>>>(a->A, a->d_pos);
-    AZ_HIP(hipGetLastError());
-    AZ_HIP(hipStreamSynchronize(a->st));
-    a->seed = seed;
-    a->start = sp;
-    a->hist.assign(G, std::vector<int32_t>());
-    a->result.assign(G, azc::ONGOING);
-    a->turn.resize(G);
-    a->fullmoves.resize(G);
-    for (int g = 0; g < G; g++) { a->turn[g] = sp[g].turn; a->fullmoves[g] = sp[g].fullmoves; }
-    a->num_inferences = a->rows = 0.0;
-    return 0;
+    return match_reset(engine(a), start, seed);
 }
 
 int az_arena_step(az_arena* a, const float* u, const int32_t* actions, int* live) {
     if (!a) return fail("az_arena_step: null arena");
-    const int G = a->A.G;
-    ArenaDev& A = a->A;
-    AZ_HIP(hipSetDevice(a->device));
-    // this ply's movers, from the host mirror
-    std::vector<int> mv[2];
-    for (int g = 0; g < G; g++)
-        if (a->result[g] == azc::ONGOING) mv[slot_of(a, g)].push_back(g);
-    if (mv[0].empty() && mv[1].empty()) {
-        if (live) *live = 0;
-        return 0;
-    }
-    std::vector<float>& hu = a->hu;
-    hu.assign(G, 0.0f);
-    for (int g = 0; g < G; g++) {
-        if (u) { hu[g] = u[g]; continue; }
-        uint64_t ctr = 0;
-        hu[g] = azc::uniform01(azc::stream_key(a->seed, (uint64_t)g, (uint64_t)a->hist[g].size(), 2), ctr);
-    }
-    std::vector<int32_t>& hact = a->hact;
-    hact.assign(G, -1);
-    bool given = false, positions = false;
-    double ninf = 0.0, nrows = 0.0;
-    for (int k = 0; k < 2; k++) {
-        if (mv[k].empty()) continue;
-        const az_arena_player& p = a->pl[k];
-        if (p.kind == AZ_PLAYER_EXTERNAL) {
-            if (!actions)
-                return fail("az_arena_step: game " + std::to_string(mv[k][0]) + " has an external mover and actions is NULL");
-            for (int g : mv[k]) hact[g] = actions[g];
-            given = true;
-        } else if (p.kind == AZ_PLAYER_MINIMAX) {
-            if (!positions) {
-                k_arena_positions<<<(G + 63) / 64, 64, 0, a->st>>>(A, a->d_pos);
-                AZ_HIP(hipGetLastError());
-                positions = true;
-            }
-            std::vector<azc::Pos> all(G);
-            AZ_HIP(hipMemcpyAsync(all.data(), a->d_pos, (size_t)G * sizeof(azc::Pos), hipMemcpyDeviceToHost, a->st));
-            AZ_HIP(hipStreamSynchronize(a->st));
-            const int n = (int)mv[k].size();
-            std::vector<azc::Pos> pos(n);
-            for (int i = 0; i < n; i++) pos[i] = all[mv[k][i]];
-            std::vector<int32_t> m((size_t)n * AZ_MAX_MOVES), pr((size_t)n * AZ_MAX_MOVES), sc((size_t)n * AZ_MAX_MOVES), nm(n);
-            if (az_minimax_scores(a->device, reinterpret_cast<const az_pos*>(pos.data()), n, p.depth, m.data(), pr.data(),
-                                  sc.data(), nm.data(), nullptr))
-                return -1;
-            for (int i = 0; i < n; i++) {
-                const int g = mv[k][i];
-                const int b = az_minimax_best(sc.data() + (size_t)i * AZ_MAX_MOVES, nm[i], hu[g]);
-                hact[g] = b >= 0 ? m[(size_t)i * AZ_MAX_MOVES + b] : -1;
-            }
-            AZ_HIP(hipSetDevice(a->device));
-            given = true;
-        } else if (p.kind == AZ_PLAYER_MCTS) {
-            // a fresh noiseless tree per move (MCTree::async_init(.., false)) through the set-roots path,
-            // from the host copy of the move lists; spare slots repeat the first game's root
-            az_search* s = a->search[k];
-            const int S = a->slots, n = (int)mv[k].size();
-            if (n > S) return fail("az_arena_step: more games to move than the MCTS player's search holds");
-            std::vector<azc::Pos> st(S);
-            std::vector<int32_t> flat, off(S + 1, 0), gid(S), nply(S);
-            for (int i = 0; i < S; i++) {
-                const int g = mv[k][i < n ? i : 0];
-                st[i] = a->start[g];
-                flat.insert(flat.end(), a->hist[g].begin(), a->hist[g].end());
-                off[i + 1] = (int32_t)flat.size();
-                gid[i] = i;
-                nply[i] = (int32_t)a->hist[g].size();
-            }
-            flat.push_back(0);
-            az_search_stats s0, s1;
-            if (az_search_stats_get(s, &s0)) return -1;
-            if (az_search_set_roots_from(s, reinterpret_cast<const az_pos*>(st.data()), flat.data(), off.data(), gid.data(),
-                                         nply.data(), 0))
-                return -1;
-            if (az_search_run(s, a->improved.data(), nullptr, nullptr)) return -1;
-            if (az_search_stats_get(s, &s1)) return -1;
-            for (int i = 0; i < n; i++) {
-                const int g = mv[k][i];
-                hact[g] = choose_host(a->improved.data() + (size_t)i * AZ_ACTION_SPACE, a->fullmoves[g],
-                                      a->cfg.num_stochastic_moves, hu[g]);
-            }
-            ninf += (double)a->cfg.sims + 1.0;
-            nrows += (double)(s1.evals - s0.evals);
-            AZ_HIP(hipSetDevice(a->device));
-            given = true;
-        }
-    }
-    AZ_HIP(hipMemsetAsync(A.io, 0, (2 + 2 * (size_t)G) * 4, a->st));
-    AZ_HIP(hipMemcpyAsync(a->d_u, hu.data(), (size_t)G * 4, hipMemcpyHostToDevice, a->st));
-    if (given) AZ_HIP(hipMemcpyAsync(a->d_act, hact.data(), (size_t)G * 4, hipMemcpyHostToDevice, a->st));
-    for (int k = 0; k < 2; k++) {
-        if (mv[k].empty() || a->pl[k].kind != AZ_PLAYER_BASE) continue;
-        const int n = (int)mv[k].size();
-        k_arena_stage<<<G, 64, 0, a->st>>>(A, k, a->d_planes[k]);
-        AZ_HIP(hipGetLastError());
-        if (az_net_forward_device(a->pl[k].net, a->d_planes[k], n, a->d_pol[k], a->d_val[k], a->st)) return -1;
-        AZ_HIP(hipSetDevice(a->device));
-        ninf += 1.0;
-        nrows += (double)n;
-    }
-    k_arena_pick<<<G, 64, 0, a->st>>>(A);
-    AZ_HIP(hipGetLastError());
-    k_arena_commit<<<G, 64, 0, a->st>>>(A);
-    AZ_HIP(hipGetLastError());
-    AZ_HIP(hipMemcpyAsync(a->io.data(), A.io, a->io.size() * 4, hipMemcpyDeviceToHost, a->st));
-    AZ_HIP(hipStreamSynchronize(a->st));
-    const int* status = a->io.data() + 2;
-    const int* chosen = a->io.data() + 2 + G;
-    const int* result = a->io.data() + 2 + 2 * G;
-    if (a->io[0]) {                                          // nothing was committed
-        for (int g = 0; g < G; g++) {
-            if (status[g] == ST_NONFINITE)
-                return fail("az_arena_step: game " + std::to_string(g) + ": the policy has a non-finite legal entry");
-            if (status[g] == ST_ILLEGAL)
-                return fail("az_arena_step: game " + std::to_string(g) + ": index " + std::to_string(chosen[g]) +
-                            " is not a legal move");
-        }
-        return fail("az_arena_step: a move was refused");
-    }
-    for (int k = 0; k < 2; k++)
-        for (int g : mv[k]) {
-            a->hist[g].push_back(chosen[g]);
-            if (a->turn[g] == 1) a->fullmoves[g]++;
-            a->turn[g] ^= 1;
-            a->result[g] = result[g];
-        }
-    a->num_inferences += ninf;
-    a->rows += nrows;
-    if (live) *live = a->io[1];
-    return 0;
+    return match_step(engine(a), u, actions, live);
 }
 
 int az_arena_results(az_arena* a, int32_t* result, int32_t* plies) {
     if (!a) return fail("az_arena_results: null arena");
-    const int G = a->A.G;
-    AZ_HIP(hipSetDevice(a->device));
-    if (result) AZ_HIP(hipMemcpyAsync(result, a->A.result(), (size_t)G * 4, hipMemcpyDeviceToHost, a->st));
-    if (plies) AZ_HIP(hipMemcpyAsync(plies, a->A.plies, (size_t)G * 4, hipMemcpyDeviceToHost, a->st));
-    AZ_HIP(hipStreamSynchronize(a->st));
-    return 0;
+    return match_results(engine(a), result, plies);
 }
 
 int az_arena_live(az_arena* a, int32_t* live) {
     if (!a || !live) return fail("az_arena_live: null argument");
-    int n = 0;
-    for (int g = 0; g < a->A.G; g++) n += live[g] = a->result[g] == azc::ONGOING ? 1 : 0;
-    return n;
+    return match_live(engine(a), live);
 }
 
 int az_arena_history(az_arena* a, int game, int32_t* moves, int cap) {
     if (!a) return fail("az_arena_history: null arena");
-    if (game < 0 || game >= a->A.G) return fail("az_arena_history: no game " + std::to_string(game));
-    AZ_HIP(hipSetDevice(a->device));
-    int n = 0;
-    AZ_HIP(hipMemcpyAsync(&n, a->A.plies + game, 4, hipMemcpyDeviceToHost, a->st));
-    AZ_HIP(hipStreamSynchronize(a->st));
-    const int m = n < cap ? n : cap;
-    if (moves && m > 0) {
-        AZ_HIP(hipMemcpyAsync(moves, a->A.moves + (size_t)game * HMAX, (size_t)m * 4, hipMemcpyDeviceToHost, a->st));
-        AZ_HIP(hipStreamSynchronize(a->st));
-    }
-    return n;
+    if (game < 0 || game >= engine(a)->G) return fail("az_arena_history: no game " + std::to_string(game));
+    return match_history(engine(a), game, moves, cap);
 }
 
 int az_arena_stats(az_arena* a, double* num_inferences, double* rows) {
     if (!a) return fail("az_arena_stats: null arena");
-    if (num_inferences) *num_inferences = a->num_inferences;
-    if (rows) *rows = a->rows;
+    return match_stats(engine(a), num_inferences, rows);
+}
+
+// ---------------------------------------------------------------- az_tournament_*: a round robin's matches
+int az_tournament_matches(int n_players) {
+    if (n_players < 2 || n_players > AZ_TOURNAMENT_MAX_PLAYERS)
+        return fail("az_tournament_matches: n_players outside 2.." + std::to_string(AZ_TOURNAMENT_MAX_PLAYERS));
+    return n_players * (n_players - 1) / 2;
+}
+
+int az_tournament_pair(int n_players, int m, int* p1, int* p2) {
+    const int M = az_tournament_matches(n_players);
+    if (M < 0) return -1;
+    if (!p1 || !p2) return fail("az_tournament_pair: null argument");
+    if (m < 0 || m >= M) return fail("az_tournament_pair: no match " + std::to_string(m));
+    int i = 1;
+    while ((i + 1) * i / 2 <= m) i++;
+    *p1 = i;
+    *p2 = m - i * (i - 1) / 2;
     return 0;
+}
+
+int az_tournament_create(const az_arena_player* players, int n_players, const az_arena_cfg* cfg, int device,
+                         az_tournament** out) {
+    if (!players || !cfg || !out) return fail("az_tournament_create: null argument");
+    const int M = az_tournament_matches(n_players);
+    if (M < 0) return fail("az_tournament_create: n_players outside 2.." + std::to_string(AZ_TOURNAMENT_MAX_PLAYERS));
+    std::vector<const az_arena_player*> pp(n_players);
+    for (int i = 0; i < n_players; i++) pp[i] = players + i;
+    std::vector<int> pair(M);
+    for (int m = 0; m < M; m++) {
+        int p1, p2;
+        az_tournament_pair(n_players, m, &p1, &p2);
+        pair[m] = p1 | (p2 << 8);
+    }
+    MatchEngine* e = nullptr;
+    if (match_create(ABI_TOURNAMENT, pp.data(), n_players, pair, cfg, device, &e)) return -1;
+    *out = reinterpret_cast<az_tournament*>(e);
+    return 0;
+}
+
+int az_tournament_destroy(az_tournament* t) { return match_destroy(engine(t)); }
+
+int az_tournament_reset(az_tournament* t, const az_pos* start, uint64_t seed) {
+    if (!t) return fail("az_tournament_reset: null tournament");
+    return match_reset(engine(t), start, seed);
+}
+
+int az_tournament_step(az_tournament* t, const float* u, int* live) {
+    if (!t) return fail("az_tournament_step: null tournament");
+    return match_step(engine(t), u, nullptr, live);
+}
+
+int az_tournament_results(az_tournament* t, int32_t* result, int32_t* plies) {
+    if (!t) return fail("az_tournament_results: null tournament");
+    return match_results(engine(t), result, plies);
+}
+
+int az_tournament_live(az_tournament* t, int32_t* live) {
+    if (!t || !live) return fail("az_tournament_live: null argument");
+    return match_live(engine(t), live);
+}
+
+int az_tournament_history(az_tournament* t, int match, int game, int32_t* moves, int cap) {
+    if (!t) return fail("az_tournament_history: null tournament");
+    MatchEngine* e = engine(t);
+    if (match < 0 || match >= e->M) return fail("az_tournament_history: no match " + std::to_string(match));
+    if (game < 0 || game >= e->G) return fail("az_tournament_history: no game " + std::to_string(game));
+    return match_history(e, match * e->G + game, moves, cap);
+}
+
+int az_tournament_stats(az_tournament* t, double* num_inferences, double* rows) {
+    if (!t) return fail("az_tournament_stats: null tournament");
+    return match_stats(engine(t), num_inferences, rows);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// arena_dev.h -- the one statement of a ply of an evaluation game (validation.rs:284-402), shared by the
-// kernels of arena.hip (two players per handle) and tournament.hip (a round robin's pairings per handle):
+// arena_dev.h -- the rules of a ply of an evaluation game (validation.rs:284-402), apart from the match
+// engine's bookkeeping in arena.hip, whose pick and commit kernels call them:
 //   arena_pick    legal moves of the position and the mover's choice among them -- a policy row under
 //                 validation.rs:297-308, a uniform entry of the legal-move list, or a given action -- and
 //                 its validation

@@ -1481,7 +1481,7 @@ int az_search_timing(az_search* s, az_timing* out, int reset, int enable) {
 
 }  // extern "C"
 
-// az_search_run for a caller that keeps the result on the device (tournament.hip): the simulations of the
+// az_search_run for a caller that keeps the result on the device (arena.hip): the simulations of the
 // roots just set, then k_readout's improved policy into d_improved [games][4096] (device memory of the
 // search's device).  Complete on return.  *evals (optional): network rows since the search was created.
 int azi::search_run_device(az_search* s, float* d_improved, unsigned long long* evals) {

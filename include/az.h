@@ -605,9 +605,10 @@ typedef struct az_arena az_arena;
  *             rule with u[g]; num_inferences += 1 per ply and net, rows += games to move
  *   MCTS      a fresh noiseless tree from the current state with its repetition history
  *             (MCTree::async_init(.., false)), `sims` simulations, the same rule over the improved policy
- *             (the f32 values az_search_read_roots returns); num_inferences += sims + 1.  The arena owns one
- *             az_search per MCTS player ((games + 1) / 2 slots, `games` when it plays both colours, no FEN
- *             cache); spare slots repeat the first game's root, and rows counts their evaluations too
+ *             (the f32 values az_search_read_roots returns; they stay on the device); num_inferences +=
+ *             sims + 1.  The arena owns one az_search per MCTS player ((games + 1) / 2 slots, `games` when it
+ *             plays both colours, no FEN cache); spare slots repeat the first game's root, and rows counts
+ *             their evaluations too
  *   MINIMAX   az_minimax_scores at `depth` on the arena's device, then az_minimax_best(scores, nmoves, u[g])
  *   RANDOM    entry min(floor(u[g] * n), n - 1) (the product in float) of az_pos_legal_indices' list
  *   EXTERNAL  actions[g]: the seat of the reference's Player::Human or any caller-side bot

@@ -172,11 +172,14 @@ def nets():
 
 
 def pairing(name, nets):
+    name = name.replace("_5games", "")
     if name == "mcts_vs_minimax2":
         return V.Player.mcts(None), V.Player.minimax(2)
     if name == "mcts_both_sides":
         p = V.Player.mcts(None)
         return p, p
+    if name == "mcts_net_vs_base":
+        return V.Player.mcts(nets[0]), V.Player.base(nets[1])
     if name == "base_vs_minimax1":
         return V.Player.base(nets[0]), V.Player.minimax(1)
     if name == "base_vs_base":
@@ -186,11 +189,15 @@ def pairing(name, nets):
 
 
 @pytest.mark.parametrize("name", ["mcts_vs_minimax2", "mcts_both_sides", "base_vs_minimax1", "base_vs_base",
-                                  "base_vs_itself"])
+                                  "base_vs_itself", "mcts_net_vs_base", "mcts_vs_minimax2_5games",
+                                  "mcts_both_sides_5games"])
 def test_engine_match_equals_host_loop(require_gpu, nets, name):
     p1, p2 = pairing(name, nets)
+    # 5 games: an MCTS player on one side holds 3 slots and moves in 2 games on the odd plies, so a spare slot
+    # repeats its first root
+    games = 5 if name.endswith("_5games") else 6
     # num_stochastic_moves 3: plies 0-5 are sampled (WeightedIndex), plies 6-23 take the last maximum
-    kw = dict(games=6, sims=8, seed=11, max_plies=24, record=True, num_stochastic_moves=3)
+    kw = dict(games=games, sims=8, seed=11, max_plies=24, record=True, num_stochastic_moves=3)
     host, hhist, hres = V.evaluate(p1, p2, engine=False, **kw)
     eng, ehist, eres = V.evaluate(p1, p2, engine=True, **kw)
     assert ehist == hhist
@@ -287,6 +294,39 @@ def test_engine_mcts_vs_random_replays_through_the_oracle(require_gpu):
             else:
                 assert ply < len(hist[g]) - 1 or result[g] is None
     assert abs(res.p1_winrate + res.p2_winrate + res.drawrate - 1.0) < 1e-9
+
+
+def test_mcts_beside_an_external_seat_replays_through_the_oracle(require_gpu):
+    """One step holds MCTS movers, whose improved policy stays on the device for the pick kernel, and an
+    external seat's given actions: every MCTS move is the oracle's search under arena_choose, every external
+    move the caller's, and the MCTS player accounts sims + 1 inferences per ply in which it moved."""
+    G, sims, seed, nsm, plies = 3, 8, 17, 2, 6                # plies 0-3 are sampled, 4-5 take the last maximum
+    arena = V.Arena(V.Player.mcts(None), V.Player.external(), games=G, sims=sims, num_stochastic_moves=nsm, seed=seed)
+    cfg = O.make_cfg(sims=sims, noise=False, seed=0, eval_kind=0)
+    states = [A.GameState() for _ in range(G)]
+    hist = [[] for _ in range(G)]
+    for ply in range(plies):
+        u = np.array([u_draw(seed, g, ply) for g in range(G)], np.float32)
+        actions = np.full(G, -1, np.int32)                   # read for the external movers only
+        for g in range(G):
+            pos = states[g].position
+            if (g % 2 == 0) == (ply % 2 == 0):               # the MCTS player is to move
+                _, imp, _, _ = O.search_game(cfg, hist[g], noise=False)
+                move = O.arena_choose(imp, pos.fullmoves, nsm, u[g])
+            else:
+                legal = pos.legal_indices()
+                move = actions[g] = int(legal[(7 * g + ply) % len(legal)])
+            hist[g].append(int(move))
+        assert arena.step(u=u, actions=actions) == G
+        assert [arena.history(g) for g in range(G)] == hist, ply
+        for g in range(G):
+            assert int(A.play_move(states[g], hist[g][-1])) == L.ONGOING
+    assert arena.stats()[0] == (sims + 1) * plies             # it moved in some game on every ply
+    one = V.Arena(V.Player.mcts(None), V.Player.external(), games=1, sims=sims, seed=seed)
+    assert one.step() == 1                                    # White: the MCTS player
+    assert one.step(actions=[A.move_to_index(52, 36, 1)]) == 1
+    assert one.step() == 1
+    assert one.stats()[0] == (sims + 1) * 2 and len(one.history(0)) == 3
 
 
 # ------------------------------------------------------------------ 5. the engine's own stream
