@@ -78,6 +78,11 @@ class AzArenaCfg(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class AzPlayerSearch(C.Structure):
+    """az_player_search: an MCTS player's own search settings; 0 = the handle's value / one leaf."""
+    _fields_ = [("sims", C.c_int), ("leaves", C.c_int), ("c_puct", C.c_float), ("reserved", C.c_int)]
+
+
 PLAYER_MCTS, PLAYER_BASE, PLAYER_MINIMAX, PLAYER_RANDOM, PLAYER_EXTERNAL = 0, 1, 2, 3, 4
 
 # az_eval_fn (include/az.h): int (*)(void* ctx, const az_pos*, int n, float* policy, float* value)
@@ -231,6 +236,10 @@ SIGNATURES = [
     ("az_tournament_live", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("az_tournament_history", C.c_int, [C.c_void_p, C.c_int, C.c_int, P(C.c_int32), C.c_int]),
     ("az_tournament_stats", C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double)]),
+    ("az_arena_create_with", C.c_int, [P(AzArenaPlayer), P(AzArenaPlayer), P(AzPlayerSearch), P(AzPlayerSearch),
+                                       P(AzArenaCfg), C.c_int, P(C.c_void_p)]),
+    ("az_tournament_create_with", C.c_int, [P(AzArenaPlayer), P(AzPlayerSearch), C.c_int, P(AzArenaCfg), C.c_int,
+                                            P(C.c_void_p)]),
 ]
 
 if not os.path.exists(LIB_PATH):

@@ -23,6 +23,9 @@ it with the same seeded uniforms and returns the same moves, results and statist
 in lockstep and each player evaluates all of its games to move at once; evaluate_round_robin and
 compute_elo_rankings(..., engine=True, tournament=True) play through it and return the pairwise matches' moves,
 results and rates.
+An MCTS player may bring its own search settings (Player.mcts(model, sims=, leaves=, c_puct=); libaz
+az_player_search): Arena, Tournament and the host loop of evaluate all honour them, and a searching ply counts
+ceil(sims / leaves) + 1 forwards.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -46,14 +49,25 @@ class EvaluationResult:             # validation.rs:12-19
 
 
 class Player:                       # validation.rs:21-27 (MctsModel, BaseModel, MiniMax, Random)
-    def __init__(self, kind, model=None, depth=None, device=None):
+    def __init__(self, kind, model=None, depth=None, device=None, sims=None, leaves=None, c_puct=None):
         assert kind in ("mcts", "base", "random", "minimax", "external")
         self.kind, self.model, self.depth, self.device = kind, model, depth, device
+        self.sims, self.leaves, self.c_puct = sims, leaves, c_puct     # an MCTS player's own search settings
 
     @staticmethod
-    def mcts(model):
-        """Player::MctsModel; model=None searches with libaz's synthetic evaluator (tests)."""
-        return Player("mcts", model)
+    def mcts(model, sims=None, leaves=None, c_puct=None):
+        """Player::MctsModel; model=None searches with libaz's synthetic evaluator (tests).  sims, leaves and
+        c_puct are this player's own search settings (az_player_search); None takes the match's sims and
+        c_puct, and one leaf per simulation step."""
+        return Player("mcts", model, sims=sims, leaves=leaves, c_puct=c_puct)
+
+    def search_settings(self, sims, c_puct):
+        """(sims, leaves, c_puct) in effect in a match created with `sims` and `c_puct`."""
+        return (self.sims or sims, self.leaves or 1, self.c_puct or c_puct)
+
+    def search_record(self):
+        """The player's az_player_search (all zero without settings of its own)."""
+        return L.AzPlayerSearch(int(self.sims or 0), int(self.leaves or 0), float(self.c_puct or 0.0), 0)
 
     @staticmethod
     def base(model):
@@ -122,9 +136,12 @@ class Arena:
             return L.AzArenaPlayer(_KINDS[p.kind], net, int(p.depth or 0))
         r1 = rec(player_1)
         r2 = r1 if player_1 is player_2 else rec(player_2)
+        s1 = player_1.search_record()
+        s2 = s1 if player_1 is player_2 else player_2.search_record()
         cfg = L.AzArenaCfg(games, sims, num_stochastic_moves, c_puct, seed)
         h = C.c_void_p()
-        L.check(L.lib.az_arena_create(C.byref(r1), C.byref(r2), C.byref(cfg), device, C.byref(h)))
+        L.check(L.lib.az_arena_create_with(C.byref(r1), C.byref(r2), C.byref(s1), C.byref(s2), C.byref(cfg), device,
+                                           C.byref(h)))
         self._h = h
 
     def __del__(self):
@@ -207,12 +224,14 @@ class Tournament:
         self._players = list(players)                 # keeps the nets alive as long as the handle
         self.matches = tournament_matches(len(self._players))
         recs = (L.AzArenaPlayer * len(self._players))()
+        search = (L.AzPlayerSearch * len(self._players))()
         for k, p in enumerate(self._players):
             net = p.model._h if p.kind in ("mcts", "base") and p.model is not None else None
             recs[k] = L.AzArenaPlayer(_KINDS[p.kind], net, int(p.depth or 0))
+            search[k] = p.search_record()
         cfg = L.AzArenaCfg(games, sims, num_stochastic_moves, c_puct, seed)
         h = C.c_void_p()
-        L.check(L.lib.az_tournament_create(recs, len(self._players), C.byref(cfg), device, C.byref(h)))
+        L.check(L.lib.az_tournament_create_with(recs, search, len(self._players), C.byref(cfg), device, C.byref(h)))
         self._h = h
 
     def __del__(self):
@@ -346,8 +365,9 @@ def evaluate(player_1, player_2, games=EVALUATION_GAMES, sims=NUM_SIMULATIONS,
     searches = {}
     for p in (player_1, player_2):
         if p.kind == "mcts" and id(p) not in searches:
-            searches[id(p)] = BatchedSearch(p.model, games=slots, device=device, sims=sims, noise=False,
-                                            cache_capacity=0)
+            ps, pk, pc = p.search_settings(sims, C_PUCT)      # the player's own sims, leaves and c_puct
+            searches[id(p)] = BatchedSearch(p.model, games=slots, device=device, sims=ps, leaves=pk, c_puct=pc,
+                                            noise=False, cache_capacity=0)
     num_inferences, rows = 0, 0
     for ply in range(max_plies):
         live = [g for g in range(G) if result[g] is None]
@@ -381,7 +401,8 @@ def evaluate(player_1, player_2, games=EVALUATION_GAMES, sims=NUM_SIMULATIONS,
                 s.set_roots(roots, apply_noise=False)
                 imp, _, _ = s.run()
                 pols = imp[:len(gs)]
-                num_inferences += sims + 1               # root batch + one batch per simulation step
+                ps, pk, _ = p.search_settings(sims, C_PUCT)
+                num_inferences += -(-ps // pk) + 1       # root batch + one batch per wave of `leaves` simulations
                 rows += s.stats()["evals"] - e0
             else:
                 x = np.concatenate([to_tensor(states[g].position) for g in gs], 0)

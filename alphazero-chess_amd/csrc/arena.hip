@@ -9,14 +9,20 @@
 //                   matches, are compacted into rows 0..n-1 (ascending in t); a base-model player's rows get
 //                   their planes (plane_value: to_tensor, chess.rs:191-245) and ONE forward of n rows follows
 //                   on the engine's stream; an MCTS player's rows are the slots of its one search, whose
-//                   improved policy (search_run_device) stays in device memory
+//                   improved policy (search_launch_device) stays in device memory
 //   k_match_pick    one wavefront per game: arena_pick (arena_dev.h) -- legal moves, the mover's choice (a
 //                   policy row under validation.rs:297-308, a uniform entry of the legal-move list, or a
 //                   given action) and its validation
 //   k_match_commit  one wavefront per game, only if every choice of every match was valid: arena_commit
-// The host keeps a mirror of results, sides to move and move lists: an MCTS player's roots are set from it
-// (az_search_set_roots_from), a MiniMax player's az_minimax_scores runs on the downloaded positions and an
-// external seat's moves are the caller's; the last two reach the kernels as given actions.
+//   k_match_roots   one wavefront per slot of an MCTS player's search: the same compaction, and slot k's root
+//                   records (position history, length, ply) copied from the game's own history in HBM
+// The host keeps a mirror of results, sides to move and move lists: a MiniMax player's az_minimax_scores runs
+// on the downloaded positions and an external seat's moves are the caller's; both reach the kernels as given
+// actions.  With AZ_ARENA_DEVICE_ROOTS=0 an MCTS player's roots are set from the mirror instead
+// (az_search_set_roots_from).
+// An MCTS player searches with its own settings (az_player_search) on its search's own stream; the searches
+// of one ply are launched first and, under AZ_ARENA_OVERLAP, run side by side -- players that name one
+// az_net in player order -- before the engine's stream waits for them and goes on to stage / pick / commit.
 // The engine is told which ABI it answers for, and only its messages depend on that.
 #include <string.h>
 
@@ -26,6 +32,12 @@
 #include "arena_dev.h"
 
 #pragma clang fp contract(off)
+
+// AZ_ARENA_OVERLAP unset: on -- faster in every repeat of every case of profiles/arena_mcts_bench.txt's leg A
+// 
+#ifndef AZ_ARENA_OVERLAP_DEFAULT
+#define AZ_ARENA_OVERLAP_DEFAULT 1
+#endif
 
 namespace azi {
 
@@ -104,6 +116,51 @@ __global__ void __launch_bounds__(64) k_match_stage(MatchDev D, int player, floa
     for (int e = lane; e < AZ_PLANES * 64; e += 64) out[e] = azc::plane_value(p, e >> 6, e & 63);
 }
 
+// The roots of `player`'s search, set where the games are.  Slot k takes the k-th game (ascending in t) in
+// which the player is to move -- k_match_stage's rows -- and a spare slot the first of them: hist[0..plies]
+// of the game copied in 16-byte pieces (only the entries that exist), hist_len = plies + 1, ply = plies,
+// game id = k.  What az_search_set_roots_from builds from the start position and the move list: match_reset
+// stores a finalized start, and arena_commit's leaf_rules leaves the flags and rep_key finalize computes.
+static_assert(sizeof(azc::Pos) % 16 == 0, "k_match_roots copies positions as uint4");
+__global__ void __launch_bounds__(64) k_match_roots(MatchDev D, int player, SearchRoots R) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    if (k >= R.slots) return;
+    const int M = D.T / D.G;
+    int seen = 0, first = -1, hit = -1;                      // wave-uniform: they come from ballots
+    for (int m = 0; m < M && hit < 0; m++) {
+        const int pr = D.pair[m];
+        if ((pr & 255) != player && (pr >> 8) != player) continue;
+        const int end = (m + 1) * D.G;
+        for (int j0 = m * D.G; j0 < end && hit < 0; j0 += 64) {
+            const int j = j0 + lane;
+            const bool same = j < end && D.tomove[j] == player;
+            const unsigned long long mask = __ballot(same);
+            if (!mask) continue;
+            if (first < 0) first = j0 + __ffsll((long long)mask) - 1;
+            const int c = __popcll(mask);
+            if (k < seen + c) {                              // the (k - seen)-th mover of this chunk
+                const bool mine = same && __popcll(mask & ((1ull << lane) - 1ull)) == k - seen;
+                hit = j0 + __ffsll((long long)__ballot(mine)) - 1;
+            }
+            seen += c;
+        }
+    }
+    if (first < 0) return;                                   // no game to move: the host launches nothing then
+    // the game's records were written by vector stores of earlier launches: keep t in a VGPR
+    const int t = vgpr_index(hit >= 0 ? hit : first);
+    const int n = min(max(D.plies[t], 0), HMAX - 1) + 1;
+    const uint4* src = reinterpret_cast<const uint4*>(D.poshist + (size_t)t * HMAX);
+    uint4* dst = reinterpret_cast<uint4*>(R.hist + (size_t)k * HMAX);
+    const int pieces = n * (int)(sizeof(azc::Pos) / 16);
+    for (int i = lane; i < pieces; i += 64) dst[i] = src[i];
+    if (lane == 0) {
+        R.hist_len[k] = n;
+        R.game_id[k] = k;
+        R.ply[k] = n - 1;
+        R.active[k] = 1;
+    }
+}
+
 __global__ void __launch_bounds__(64) k_match_pick(MatchDev D) {
     __shared__ PickShared S;
     const int t = vgpr_index(blockIdx.x), lane = threadIdx.x;
@@ -153,6 +210,11 @@ struct MatchEngine {
     std::vector<az_arena_player> pl;
     std::vector<int> pair;              // [M] as MatchDev::pair
     std::vector<az_search*> search;     // [P], MCTS players only
+    std::vector<az_player_search> ss;   // [P] an MCTS player's settings in effect (sims, leaves >= 1, c_puct)
+    std::vector<SearchRoots> roots;     // [P] where the search's root records live, and its stream
+    std::vector<hipEvent_t> done;       // [P] recorded behind the search's readout
+    bool device_roots = true;           // AZ_ARENA_DEVICE_ROOTS: k_match_roots, else the host mirror's move lists
+    bool overlap = AZ_ARENA_OVERLAP_DEFAULT != 0;   // AZ_ARENA_OVERLAP: a ply's searches side by side
     std::vector<unsigned long long> evals;   // [P] the search's evaluations when it last ran
     std::vector<int> rows_cap;          // [P] rows of the player's part of d_pol (an MCTS player's slots)
     std::vector<float*> d_planes, d_val;
@@ -187,8 +249,8 @@ std::string game_name(const MatchEngine* e, int t) {
     return e->abi == ABI_ARENA ? game : "match " + std::to_string(t / e->G) + " " + game;
 }
 
-int player_ok(Abi abi, const az_arena_player* p, int i) {
-    const std::string fn = fn_name(abi, "create"), which = player_name(abi, i);
+int player_ok(Abi abi, const char* call, const az_arena_player* p, int i) {
+    const std::string fn = fn_name(abi, call), which = player_name(abi, i);
     if (!p) return fail(fn + "null " + which);
     if (p->kind == AZ_PLAYER_EXTERNAL && abi == ABI_TOURNAMENT)
         return fail(fn + which + " is external; a tournament has no such seat");
@@ -198,6 +260,24 @@ int player_ok(Abi abi, const az_arena_player* p, int i) {
         return fail(fn + "MiniMax depth of " + which + " outside 1.." + std::to_string(AZ_MINIMAX_MAX_DEPTH));
     if ((p->kind == AZ_PLAYER_BASE || p->kind == AZ_PLAYER_MCTS) && p->net && !p->net->dev)
         return fail(fn + which + " has a dead net");
+    return 0;
+}
+
+// an MCTS player's own settings, as given (s may be nullptr: all zero)
+int search_ok(Abi abi, const char* call, const az_arena_player* p, const az_player_search* s, int i) {
+    if (!s) return 0;
+    const std::string fn = fn_name(abi, call), which = player_name(abi, i);
+    if (s->reserved != 0) return fail(fn + "reserved of " + which + "'s search settings must be 0");
+    if (s->sims < 0) return fail(fn + "sims of " + which + " is negative");
+    if (s->sims > 60000) return fail(fn + "sims of " + which + " above 60000");
+    if (s->leaves < 0 || s->leaves > LEAVES_MAX)
+        return fail(fn + "leaves of " + which + " outside 0.." + std::to_string(LEAVES_MAX));
+    if (!(s->c_puct >= 0.0f) || s->c_puct > 3.4028234e38f)
+        return fail(fn + "c_puct of " + which + " is negative or not finite");
+    if (p->kind != AZ_PLAYER_MCTS) {
+        const char* field = s->sims ? "sims" : s->leaves ? "leaves" : s->c_puct != 0.0f ? "c_puct" : nullptr;
+        if (field) return fail(fn + which + " is not an MCTS player and has search settings (" + field + ")");
+    }
     return 0;
 }
 
@@ -216,6 +296,7 @@ int match_destroy(MatchEngine* e) {
     (void)hipSetDevice(e->device);
     if (e->st) (void)hipStreamSynchronize(e->st);
     for (az_search* s : e->search) if (s) az_search_destroy(s);
+    for (hipEvent_t ev : e->done) if (ev) (void)hipEventDestroy(ev);
     for (void* p : e->bufs) (void)hipFree(p);
     if (e->st) (void)hipStreamDestroy(e->st);
     delete e;
@@ -268,17 +349,33 @@ int match_reset(MatchEngine* e, const az_pos* start, uint64_t seed) {
     return 0;
 }
 
-// players [P] (checked here, before the first device call); pair [M] as MatchDev::pair
-int match_create(Abi abi, const az_arena_player* const* players, int P, const std::vector<int>& pair,
-                 const az_arena_cfg* cfg, int device, MatchEngine** out) {
-    const std::string fn = fn_name(abi, "create");
-    bool mcts = false;
+// players [P] and their search settings [P] (nullptr, or entries that may be nullptr: all zero), checked here,
+// before the first device call; pair [M] as MatchDev::pair; call: "create" or "create_with", for the messages
+int match_create(Abi abi, const char* call, const az_arena_player* const* players,
+                 const az_player_search* const* search, int P, const std::vector<int>& pair, const az_arena_cfg* cfg,
+                 int device, MatchEngine** out) {
+    const std::string fn = fn_name(abi, call);
+    bool mcts = false, own = false;
     for (int i = 0; i < P; i++) {
-        if (player_ok(abi, players[i], i)) return -1;
+        if (player_ok(abi, call, players[i], i)) return -1;
+        if (search && search_ok(abi, call, players[i], search[i], i)) return -1;
         mcts |= players[i]->kind == AZ_PLAYER_MCTS;
+        own |= search && search[i];
     }
     if (cfg->games <= 0) return fail(fn + "games must be positive");
-    if (mcts && cfg->sims <= 0) return fail(fn + "an MCTS player needs sims > 0");
+    if (mcts && !own && cfg->sims <= 0) return fail(fn + "an MCTS player needs sims > 0");
+    if (own && (cfg->sims < 0 || cfg->sims > 60000)) return fail(fn + "cfg->sims outside 0..60000");
+    // the settings in effect: a field left 0 is the handle's, or one leaf
+    std::vector<az_player_search> ss(P, az_player_search{0, 0, 0.0f, 0});
+    for (int i = 0; i < P; i++) {
+        if (players[i]->kind != AZ_PLAYER_MCTS) continue;
+        const az_player_search* s = search ? search[i] : nullptr;
+        ss[i].sims = s && s->sims ? s->sims : cfg->sims;
+        ss[i].leaves = s && s->leaves ? s->leaves : 1;
+        ss[i].c_puct = s && s->c_puct != 0.0f ? s->c_puct : cfg->c_puct;
+        if (ss[i].sims <= 0)
+            return fail(fn + "sims of " + player_name(abi, i) + " is 0: neither its own nor cfg->sims is set");
+    }
     for (int i = 0; i < P; i++) {
         const az_arena_player& p = *players[i];
         if (p.net && (p.kind == AZ_PLAYER_BASE || p.kind == AZ_PLAYER_MCTS) && p.net->dev->device != device)
@@ -297,6 +394,11 @@ int match_create(Abi abi, const az_arena_player* const* players, int P, const st
     for (int i = 0; i < P; i++) e->pl.push_back(*players[i]);
     e->pair = pair;
     e->search.assign(P, nullptr);
+    e->ss = ss;
+    e->roots.assign(P, SearchRoots{});
+    e->done.assign(P, nullptr);
+    if (const char* v = getenv("AZ_ARENA_DEVICE_ROOTS")) e->device_roots = atoi(v) != 0;
+    if (const char* v = getenv("AZ_ARENA_OVERLAP")) e->overlap = atoi(v) != 0;
     e->evals.assign(P, 0ull);
     e->rows_cap.assign(P, 0);
     e->d_planes.assign(P, nullptr);
@@ -346,8 +448,9 @@ int match_create(Abi abi, const az_arena_player* const* players, int P, const st
                 az_search_cfg sc;
                 az_search_default_cfg(&sc);
                 sc.games = e->rows_cap[i];
-                sc.sims = cfg->sims;
-                sc.c_puct = cfg->c_puct;
+                sc.sims = e->ss[i].sims;
+                sc.c_puct = e->ss[i].c_puct;
+                sc.leaves = e->ss[i].leaves;
                 sc.noise = 0;
                 sc.seed = cfg->seed;
                 sc.evaluator = p.net ? AZ_EVAL_NET : AZ_EVAL_SYNTHETIC;
@@ -356,6 +459,8 @@ int match_create(Abi abi, const az_arena_player* const* players, int P, const st
                 sc.eval_log_cap = 0;
                 sc.cache_capacity = 0;
                 if (az_search_create(p.net, &sc, device, &e->search[i])) return -1;
+                if (search_roots(e->search[i], &e->roots[i])) return -1;
+                AZ_HIP(hipEventCreateWithFlags(&e->done[i], hipEventDisableTiming));
             }
         }
         e->io.resize(2 + 3 * (size_t)T);
@@ -385,6 +490,14 @@ int match_step(MatchEngine* e, const float* u, const int32_t* actions, int* live
         if (live) *live = 0;
         return 0;
     }
+    // what can refuse the step on the host is checked before any search is launched
+    for (int i = 0; i < P; i++) {
+        if (mv[i].empty()) continue;
+        if (e->pl[i].kind == AZ_PLAYER_EXTERNAL && !actions)
+            return fail(fn + game_name(e, mv[i][0]) + " has an external mover and actions is NULL");
+        if (e->pl[i].kind == AZ_PLAYER_MCTS && (int)mv[i].size() > e->rows_cap[i])
+            return fail(fn + "more games to move than the MCTS player's search holds");
+    }
     std::vector<float>& hu = e->hu;
     hu.assign(T, 0.0f);
     for (int t = 0; t < T; t++) {
@@ -398,11 +511,11 @@ int match_step(MatchEngine* e, const float* u, const int32_t* actions, int* live
     std::vector<int32_t>& hact = e->hact;
     hact.assign(T, -1);
     bool given = false, positions = false;
+    std::vector<int> launched;                               // the MCTS players searching this ply, in order
     for (int i = 0; i < P; i++) {
         if (mv[i].empty()) continue;
         const az_arena_player& p = e->pl[i];
         if (p.kind == AZ_PLAYER_EXTERNAL) {
-            if (!actions) return fail(fn + game_name(e, mv[i][0]) + " has an external mover and actions is NULL");
             for (int t : mv[i]) hact[t] = actions[t];
             given = true;
         } else if (p.kind == AZ_PLAYER_MINIMAX) {
@@ -429,34 +542,47 @@ int match_step(MatchEngine* e, const float* u, const int32_t* actions, int* live
             AZ_HIP(hipSetDevice(e->device));
             given = true;
         } else if (p.kind == AZ_PLAYER_MCTS) {
-            // a fresh noiseless tree per move (MCTree::async_init(.., false)) through the set-roots path,
-            // from the host copy of the move lists; spare slots repeat the player's first root
+            // a fresh noiseless tree per move (MCTree::async_init(.., false)); spare slots repeat the player's
+            // first root.  Everything goes to the search's own stream; nothing here waits for it
             az_search* s = e->search[i];
             const int S = e->rows_cap[i], n = (int)mv[i].size();
-            if (n > S) return fail(fn + "more games to move than the MCTS player's search holds");
-            std::vector<azc::Pos> st(S);
-            std::vector<int32_t> flat, off(S + 1, 0), gid(S), nply(S);
-            for (int k = 0; k < S; k++) {
-                const int t = mv[i][k < n ? k : 0];
-                st[k] = e->start[t % G];
-                flat.insert(flat.end(), e->hist[t].begin(), e->hist[t].end());
-                off[k + 1] = (int32_t)flat.size();
-                gid[k] = k;
-                nply[k] = (int32_t)e->hist[t].size();
+            // two searches on one az_net stay one after the other, in player order
+            if (p.net)
+                for (int j : launched)
+                    if (e->pl[j].net == p.net) AZ_HIP(hipStreamWaitEvent(e->roots[i].st, e->done[j], 0));
+            if (e->device_roots) {
+                k_match_roots<<<S, 64, 0, e->roots[i].st>>>(D, i, e->roots[i]);
+                AZ_HIP(hipGetLastError());
+                if (search_set_roots_device(s)) return -1;
+            } else {                                         // from the host copy of the move lists
+                std::vector<azc::Pos> st(S);
+                std::vector<int32_t> flat, off(S + 1, 0), gid(S), nply(S);
+                for (int k = 0; k < S; k++) {
+                    const int t = mv[i][k < n ? k : 0];
+                    st[k] = e->start[t % G];
+                    flat.insert(flat.end(), e->hist[t].begin(), e->hist[t].end());
+                    off[k + 1] = (int32_t)flat.size();
+                    gid[k] = k;
+                    nply[k] = (int32_t)e->hist[t].size();
+                }
+                flat.push_back(0);
+                if (az_search_set_roots_from(s, reinterpret_cast<const az_pos*>(st.data()), flat.data(), off.data(),
+                                             gid.data(), nply.data(), 0))
+                    return -1;
             }
-            flat.push_back(0);
-            if (az_search_set_roots_from(s, reinterpret_cast<const az_pos*>(st.data()), flat.data(), off.data(), gid.data(),
-                                         nply.data(), 0))
-                return -1;
-            unsigned long long ev = 0;
-            if (search_run_device(s, e->d_pol + (size_t)D.pl[i].row_base * AZ_ACTION_SPACE, &ev)) return -1;
+            if (search_launch_device(s, e->d_pol + (size_t)D.pl[i].row_base * AZ_ACTION_SPACE, e->done[i])) return -1;
+            launched.push_back(i);
+            if (!e->overlap && search_finish_device(s, nullptr)) return -1;   // one after the other
             AZ_HIP(hipSetDevice(e->device));
-            ninf += (double)e->cfg.sims + 1.0;
-            nrows += (double)(ev - e->evals[i]);
-            e->evals[i] = ev;
-            k_match_stage<<<T, 64, 0, e->st>>>(D, i, nullptr);   // the games' slot rows
-            AZ_HIP(hipGetLastError());
+            // the forwards it launches: the root batch and one per wave of `leaves` simulations
+            ninf += (double)((e->ss[i].sims + e->ss[i].leaves - 1) / e->ss[i].leaves) + 1.0;
         }
+    }
+    // the engine's stream goes on behind every search of the ply
+    for (int i : launched) {
+        AZ_HIP(hipStreamWaitEvent(e->st, e->done[i], 0));
+        k_match_stage<<<T, 64, 0, e->st>>>(D, i, nullptr);   // the games' slot rows
+        AZ_HIP(hipGetLastError());
     }
     // one stage launch and one forward per base-model player, over its games to move in all its matches
     for (int i = 0; i < P; i++) {
@@ -479,6 +605,13 @@ int match_step(MatchEngine* e, const float* u, const int32_t* actions, int* live
     AZ_HIP(hipGetLastError());
     AZ_HIP(hipMemcpyAsync(e->io.data(), D.io, e->io.size() * 4, hipMemcpyDeviceToHost, e->st));
     AZ_HIP(hipStreamSynchronize(e->st));
+    for (int i : launched) {                                 // rows: the searches' evaluations
+        unsigned long long ev = 0;
+        if (search_finish_device(e->search[i], &ev)) return -1;
+        nrows += (double)(ev - e->evals[i]);
+        e->evals[i] = ev;
+    }
+    AZ_HIP(hipSetDevice(e->device));
     const int* status = e->io.data() + 2;
     const int* chosen = e->io.data() + 2 + T;
     const int* result = e->io.data() + 2 + 2 * T;
@@ -566,15 +699,35 @@ int az_arena_choose(const float* policy, int fullmoves, int num_stochastic_moves
     return AZ_ACTION_SPACE - 1;
 }
 
-int az_arena_create(const az_arena_player* p1, const az_arena_player* p2, const az_arena_cfg* cfg, int device,
-                    az_arena** out) {
-    if (!cfg || !out) return fail("az_arena_create: null argument");
+static int arena_create(const char* call, const az_arena_player* p1, const az_arena_player* p2,
+                        const az_player_search* s1, const az_player_search* s2, const az_arena_cfg* cfg, int device,
+                        az_arena** out) {
+    const std::string fn = std::string("az_arena_") + call + ": ";
+    if (!cfg || !out) return fail(fn + "null argument");
     const az_arena_player* players[2] = {p1, p2};
+    const az_player_search* search[2] = {s1, s2};
     const bool same = p1 && p1 == p2;                        // one player on both sides: pair (0, 0), else (0, 1)
+    if (same && s2 && s2 != s1) {
+        const az_player_search zero{0, 0, 0.0f, 0};
+        if (memcmp(s2, s1 ? s1 : &zero, sizeof(zero)) != 0)
+            return fail(fn + "one player on both sides, and the search settings of player 2 differ from player 1's");
+    }
     MatchEngine* e = nullptr;
-    if (match_create(ABI_ARENA, players, same ? 1 : 2, {same ? 0 : 1 << 8}, cfg, device, &e)) return -1;
+    if (match_create(ABI_ARENA, call, players, s1 || s2 ? search : nullptr, same ? 1 : 2, {same ? 0 : 1 << 8}, cfg, device,
+                     &e))
+        return -1;
     *out = reinterpret_cast<az_arena*>(e);
     return 0;
+}
+
+int az_arena_create(const az_arena_player* p1, const az_arena_player* p2, const az_arena_cfg* cfg, int device,
+                    az_arena** out) {
+    return arena_create("create", p1, p2, nullptr, nullptr, cfg, device, out);
+}
+
+int az_arena_create_with(const az_arena_player* p1, const az_arena_player* p2, const az_player_search* s1,
+                         const az_player_search* s2, const az_arena_cfg* cfg, int device, az_arena** out) {
+    return arena_create("create_with", p1, p2, s1, s2, cfg, device, out);
 }
 
 int az_arena_destroy(az_arena* a) { return match_destroy(engine(a)); }
@@ -629,13 +782,18 @@ int az_tournament_pair(int n_players, int m, int* p1, int* p2) {
     return 0;
 }
 
-int az_tournament_create(const az_arena_player* players, int n_players, const az_arena_cfg* cfg, int device,
-                         az_tournament** out) {
-    if (!players || !cfg || !out) return fail("az_tournament_create: null argument");
+static int tournament_create(const char* call, const az_arena_player* players, const az_player_search* search,
+                             int n_players, const az_arena_cfg* cfg, int device, az_tournament** out) {
+    const std::string fn = std::string("az_tournament_") + call + ": ";
+    if (!players || !cfg || !out) return fail(fn + "null argument");
     const int M = az_tournament_matches(n_players);
-    if (M < 0) return fail("az_tournament_create: n_players outside 2.." + std::to_string(AZ_TOURNAMENT_MAX_PLAYERS));
+    if (M < 0) return fail(fn + "n_players outside 2.." + std::to_string(AZ_TOURNAMENT_MAX_PLAYERS));
     std::vector<const az_arena_player*> pp(n_players);
-    for (int i = 0; i < n_players; i++) pp[i] = players + i;
+    std::vector<const az_player_search*> sp(n_players);
+    for (int i = 0; i < n_players; i++) {
+        pp[i] = players + i;
+        sp[i] = search ? search + i : nullptr;
+    }
     std::vector<int> pair(M);
     for (int m = 0; m < M; m++) {
         int p1, p2;
@@ -643,9 +801,20 @@ int az_tournament_create(const az_arena_player* players, int n_players, const az
         pair[m] = p1 | (p2 << 8);
     }
     MatchEngine* e = nullptr;
-    if (match_create(ABI_TOURNAMENT, pp.data(), n_players, pair, cfg, device, &e)) return -1;
+    if (match_create(ABI_TOURNAMENT, call, pp.data(), search ? sp.data() : nullptr, n_players, pair, cfg, device, &e))
+        return -1;
     *out = reinterpret_cast<az_tournament*>(e);
     return 0;
+}
+
+int az_tournament_create(const az_arena_player* players, int n_players, const az_arena_cfg* cfg, int device,
+                         az_tournament** out) {
+    return tournament_create("create", players, nullptr, n_players, cfg, device, out);
+}
+
+int az_tournament_create_with(const az_arena_player* players, const az_player_search* search, int n_players,
+                              const az_arena_cfg* cfg, int device, az_tournament** out) {
+    return tournament_create("create_with", players, search, n_players, cfg, device, out);
 }
 
 int az_tournament_destroy(az_tournament* t) { return match_destroy(engine(t)); }

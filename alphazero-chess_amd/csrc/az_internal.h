@@ -332,4 +332,23 @@ namespace azi {
 // the search's device -- the simulations of the roots just set, then k_readout.  Complete on return.
 // *evals (may be nullptr): the network rows the search has evaluated since it was created
 int search_run_device(az_search* s, float* d_improved, unsigned long long* evals);
+
+// The same search in parts, for a caller that sets the roots with a kernel of its own and runs several
+// searches side by side (arena.hip).  Where a search's root records live and the stream its work runs on:
+struct SearchRoots {
+    int slots;                             // az_search_cfg.games
+    azc::Pos* hist; int* hist_len;         // [slots][HMAX], [slots]: Engine::hist / hist_len
+    int* game_id; int* ply; int* active;   // [slots]
+    hipStream_t st;
+};
+int search_roots(az_search* s, SearchRoots* out);
+// after the caller's launches on SearchRoots::st have written every slot's records: what
+// az_search_set_roots_from(.., apply_noise = 0) does behind its upload (k_root_setup, the root evaluation,
+// k_root_noise(0)), queued on that stream with no host synchronise.  AZ_EVAL_NET / AZ_EVAL_SYNTHETIC only
+int search_set_roots_device(az_search* s);
+// search_run_device's launches: the simulations, k_readout into d_improved, then `done` recorded on the
+// search's stream
+int search_launch_device(az_search* s, float* d_improved, hipEvent_t done);
+// ... and its read-back of `evals`; waits for the search's stream
+int search_finish_device(az_search* s, unsigned long long* evals);
 }  // namespace azi

@@ -1502,3 +1502,62 @@ int azi::search_run_device(az_search* s, float* d_improved, unsigned long long* 
     }
     return 0;
 }
+
+// ---------------------------------------------------------------- the same search in parts (arena.hip)
+int azi::search_roots(az_search* s, SearchRoots* out) {
+    if (!s || !out) return fail("search_roots: null argument");
+    const Engine& E = s->E;
+    out->slots = E.G;
+    out->hist = E.hist; out->hist_len = E.hist_len;
+    out->game_id = E.game_id; out->ply = E.ply; out->active = E.active;
+    out->st = s->st;
+    return 0;
+}
+
+// setup_roots(s, 0, false) behind az_search_set_roots_from, without its closing synchronise: the caller's
+// launches, these and the simulations are ordered by the search's stream
+int azi::search_set_roots_device(az_search* s) {
+    if (!s) return fail("search_set_roots_device: null search");
+    if (s->cfg.evaluator != AZ_EVAL_NET && s->cfg.evaluator != AZ_EVAL_SYNTHETIC)
+        return fail("search_set_roots_device: a callback evaluator's roots go through az_search_set_roots");
+    AZ_HIP(hipSetDevice(s->device));
+    if (adopt_net_generation(s)) return -1;
+    Engine& E = s->E;
+    s->sim_cursor = 0;
+    s->roots_fresh = false;
+    AZ_HIP(hipMemsetAsync(E.ctr->batch_count, 0, sizeof(E.ctr->batch_count), s->st));
+    k_root_setup<<<(E.G + 63) / 64, 64, 0, s->st>>>(E);
+    int rc = eval_rows(s);
+    if (rc) return rc;
+    AZ_HIP(hipMemsetAsync(E.ctr->batch_count, 0, sizeof(int), s->st));   // simulation step 0 allocates from [0]
+    k_root_noise<<<E.G, 64, 0, s->st>>>(E, 0);
+    AZ_HIP(hipGetLastError());
+    s->roots_fresh = true;
+    return 0;
+}
+
+int azi::search_launch_device(az_search* s, float* d_improved, hipEvent_t done) {
+    if (!s || !d_improved || !done) return fail("search_launch_device: null argument");
+    if (check_net_generation(s, "search_launch_device")) return -1;
+    if (!s->roots_fresh) return fail("search_launch_device: set roots first");
+    s->roots_fresh = false;
+    AZ_HIP(hipSetDevice(s->device));
+    int rc = run_sims(s);
+    if (rc) return rc;
+    k_readout<<<s->E.G, 256, 0, s->st>>>(s->E, d_improved, nullptr, nullptr);
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipEventRecord(done, s->st));
+    return 0;
+}
+
+int azi::search_finish_device(az_search* s, unsigned long long* evals) {
+    if (!s) return fail("search_finish_device: null search");
+    AZ_HIP(hipSetDevice(s->device));
+    AZ_HIP(hipStreamSynchronize(s->st));
+    if (evals) {
+        Counters c;
+        AZ_HIP(hipMemcpy(&c, s->E.ctr, sizeof(c), hipMemcpyDeviceToHost));
+        *evals = c.evals + sum_games(s, s->E.g_evals);
+    }
+    return 0;
+}

@@ -686,6 +686,30 @@ int az_tournament_history(az_tournament* t, int match, int game, int32_t* moves,
 /* forwards launched and rows evaluated by the whole tournament since the last reset */
 int az_tournament_stats(az_tournament* t, double* num_inferences, double* rows);
 
+/* ---- an MCTS player's own search settings ----------------------------------------------------------
+ * A field left 0 takes the handle's az_arena_cfg value (sims, c_puct) or the default (leaves: 1, the
+ * reference's search; 2..8: az_search_cfg.leaves).  16 bytes.  The player's az_search is created with its own
+ * sims, c_puct and leaves -- its node and edge arenas follow its sims, its slots are what they are without
+ * settings -- and a ply it searches adds ceil(sims / leaves) + 1 to num_inferences: the forwards it launches,
+ * sims + 1 at one leaf.  rows stays the search's evaluations. */
+typedef struct { int sims; int leaves; float c_puct; int reserved; } az_player_search;
+/* az_arena_create with s1 / s2 the settings of p1 / p2; either may be NULL (all zero).  Refused, before the
+ * first device call and with *out untouched, in a message naming the player and the field: leaves outside
+ * 0..8, sims < 0, c_puct < 0 or not finite, reserved != 0, a non-zero field on a player that is not
+ * AZ_PLAYER_MCTS, an MCTS player whose sims come out 0 (cfg->sims may be 0 when every MCTS player brings its
+ * own), and, with p1 == p2, an s2 that is neither NULL nor equal to *s1.  az_arena_create is this call with
+ * NULL, NULL.
+ * Environment, read here: AZ_ARENA_DEVICE_ROOTS (unset or 1: an MCTS player's roots are written by a kernel
+ * from the arena's own position histories; 0: replayed on the host and uploaded) and AZ_ARENA_OVERLAP (unset
+ * or 1: the searches of one ply run side by side on their own streams, players that name one az_net in player
+ * order; 0: one after the other).  Every combination plays the same games and reports the same statistics. */
+int az_arena_create_with(const az_arena_player* p1, const az_arena_player* p2, const az_player_search* s1,
+                         const az_player_search* s2, const az_arena_cfg* cfg, int device, az_arena** out);
+/* az_tournament_create with search [n_players] (NULL: all zero): search[i] belongs to players[i].  The same
+ * refusals and the same environment; az_tournament_create is this call with NULL. */
+int az_tournament_create_with(const az_arena_player* players, const az_player_search* search, int n_players,
+                              const az_arena_cfg* cfg, int device, az_tournament** out);
+
 #ifdef __cplusplus
 }
 #endif
