@@ -157,6 +157,8 @@ SIGNATURES = [
     ("az_search_stats_get", C.c_int, [C.c_void_p, P(AzSearchStats)]),
     ("az_search_persistent", C.c_int, [C.c_void_p]),
     ("az_search_leaf_stats", C.c_int, [C.c_void_p, P(C.c_int), P(C.c_uint64)]),
+    ("az_search_set_tree_reuse", C.c_int, [C.c_void_p, C.c_int]),
+    ("az_search_reuse_stats", C.c_int, [C.c_void_p, P(C.c_int), P(C.c_uint64), P(C.c_uint64), P(C.c_uint64)]),
     ("az_search_eval_log", C.c_int, [C.c_void_p, P(C.c_int64), P(C.c_int64), P(C.c_uint64), P(C.c_float),
                                      P(C.c_int32), P(C.c_int32), P(C.c_float)]),
     ("az_search_timing", C.c_int, [C.c_void_p, P(AzTiming), C.c_int, C.c_int]),

@@ -45,11 +45,20 @@ def _convert(st):
 
 
 class SelfPlay:
-    """run_all_episodes engine: G game slots on one GPU."""
+    """run_all_episodes engine: G game slots on one GPU.  tree_reuse=True (BatchedSearch): a game's
+    re-roots keep the played move's subtree."""
 
-    def __init__(self, model=None, games=100, device=0, continuous=False, **cfg):
-        self.search = BatchedSearch(model, games=games, device=device, continuous=continuous, **cfg)
+    def __init__(self, model=None, games=100, device=0, continuous=False, tree_reuse=False, **cfg):
+        self.search = BatchedSearch(model, games=games, device=device, continuous=continuous,
+                                    tree_reuse=tree_reuse, **cfg)
         self.games = games
+
+    @property
+    def tree_reuse(self):
+        return self.search.tree_reuse
+
+    def reuse_stats(self):
+        return self.search.reuse_stats()
 
     def reset(self):
         self.search.check(L.lib.az_selfplay_reset(self.search._h))
@@ -112,11 +121,13 @@ class SelfPlay:
         return (L.AzEpisodeStep * sum(len(p) for p in parts))(*[s for p in parts for s in p])
 
 
-def run_all_episodes(model=None, games=100, max_moves=1000, device=0, **cfg):
+def run_all_episodes(model=None, games=100, max_moves=1000, device=0, tree_reuse=False, **cfg):
     """training.rs:340-378: play `games` games from startpos to the end; returns
     (avg_batch_size, steps) like the reference (steps of all games, game order).  avg_batch_size is network
-    rows per simulation step launched; with leaves=K a step is a wave of up to K simulations per game."""
-    sp = SelfPlay(model, games=games, device=device, continuous=False, **cfg)
+    rows per simulation step launched; with leaves=K a step is a wave of up to K simulations per game.
+    tree_reuse=True (SelfPlay): re-roots keep the played move's subtree; avg_batch_size is then rows per
+    simulation run per game, the games that need fewer steps in a move counted as they ran."""
+    sp = SelfPlay(model, games=games, device=device, continuous=False, tree_reuse=tree_reuse, **cfg)
     sp.reset()
     steps = []
     for _ in range(max_moves):
@@ -428,7 +439,7 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
           allgather=None, log=None, log_batch=None, device_replay=False, elo_evaluator=None,
           elo_games=EVALUATION_GAMES, elo_base=150.0, gate=False, gate_threshold=WIN_RATE_THRESHOLD,
           gate_games=EVALUATION_GAMES, log_gate=None, save_dir=None, carry_games=False, games_per_iteration=None,
-          log_selfplay=None, log_adopt=None):
+          log_selfplay=None, log_adopt=None, tree_reuse=False):
     """train() (training.rs:39-275) without the TUI.  Per iteration: self-play `games` games with
     model.valid() until the replay buffer holds min_replay unique positions, then train_steps AdamW
     steps on batches of batch_size at get_cyclical_lr(iteration); the new model replaces the old one.
@@ -496,6 +507,10 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
     neither the buffer nor the caller, and the return shape does not change.  One rank only for now
     (world > 1 raises ValueError); device_replay, elo_evaluator, gate, save_dir and dtype combine with it
     unchanged.
+    tree_reuse (opt-in; False: untouched): every SelfPlay handle of the run, the carry_games one included,
+    is created with tree_reuse=True (SelfPlay; weight adoption still discards the carried subtrees).  The
+    entry gains `selfplay_carried_visits`, the visits the iteration's re-roots kept; `selfplay_sims` stays
+    the simulations run.
     Returns (trainer, replay, per-iteration stats)."""
     from .memory import ReplayBuffer, add_from_ranks
     if comm and reducer:
@@ -534,12 +549,13 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
             model = trainer.model(dtype, into=model)   # created once, then refreshed in place on the device
         new_unique, plays, sims_done, games_done, steps_done, moves_done, finished = 0, 0, 0, 0, 0, 0, 0
         steps_global = 0
+        carried_visits = 0
         carry = {}
         if carry_games:
             ta = time.perf_counter()
             if carried is None:
                 carried = SelfPlay(model, games=games, sims=sims, device=device, continuous=True,
-                                   seed=seed + 1000003 * rank)
+                                   seed=seed + 1000003 * rank, tree_reuse=tree_reuse)
                 carried.reset()
                 carry = {"carried_in": 0, "adopt_s": 0.0}
             else:
@@ -550,6 +566,7 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
                 if log_adopt:
                     log_adopt(iteration, flight, trainer)
             s0 = carried.search.stats()   # after the adoption: its root rows are not self-play batches
+            r0 = carried.reuse_stats() if tree_reuse else None
         while carry_games:              # passes of the carried pool (the lockstep passes are the loop below)
             done = 0
             while done < carry_target:
@@ -567,10 +584,12 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
                 sims_done, moves_done = ss["sims"] - s0["sims"], ss["moves"] - s0["moves"]
                 finished = games_done = ss["games_finished"] - s0["games_finished"]
                 carry["selfplay_avg_batch"] = (ss["evals"] - s0["evals"]) / max(sims_done / games, 1)
+                if tree_reuse:
+                    carried_visits += carried.reuse_stats()["carried_visits"] - r0["carried_visits"]
                 break
         while not carry_games:
             sp = SelfPlay(model, games=games, sims=sims, device=device, continuous=False,
-                          seed=seed + 1000003 * rank + 7919 * iteration + 104729 * plays)
+                          seed=seed + 1000003 * rank + 7919 * iteration + 104729 * plays, tree_reuse=tree_reuse)
             sp.reset()
             local = []
             while True:
@@ -599,6 +618,8 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
             moves_done += ss["moves"]
             finished += ss["games_finished"]
             games_done += games
+            if tree_reuse:
+                carried_visits += sp.reuse_stats()["carried_visits"]
             if len(replay) >= min_replay:   # the global length when the buffer is shared
                 break
         t1 = time.perf_counter()
@@ -646,6 +667,8 @@ def train(iterations, blocks=NUM_RES_BLOCKS, filters=NUM_FILTERS, games=NUM_EPIS
               "shared_replay": shared_replay and world > 1, "shard_batch": shard_batch,
               "episode_steps_global": steps_global if shared_replay and world > 1 else steps_done}
         st.update(carry)
+        if tree_reuse:
+            st["selfplay_carried_visits"] = carried_visits
         accepted, t3 = True, t2
         if gate:   # training.rs:208-232
             from .validation import Player, evaluate

@@ -47,9 +47,13 @@ def _eval_trampoline(evaluator):
 class BatchedSearch:
     """G concurrent game trees on one device."""
 
-    def __init__(self, model=None, games=1, device=0, evaluator=None, **cfg):
+    def __init__(self, model=None, games=1, device=0, evaluator=None, tree_reuse=False, **cfg):
         """model: an AlphaZero (AZ_EVAL_NET); evaluator: a caller-owned process_batch-style callable
-        (AZ_EVAL_CALLBACK); neither: the synthetic evaluator the oracle shares."""
+        (AZ_EVAL_CALLBACK); neither: the synthetic evaluator the oracle shares.
+        tree_reuse (opt-in; False: every re-root starts from an empty tree, the reference's traverse_new):
+        advance() and the self-play driver keep the played move's subtree and a move's search tops the
+        root up to `sims` visits (az_search_set_tree_reuse).  A different search from the reference's;
+        not with leaves > 1."""
         synthetic = model is None and evaluator is None
         self.cfg = make_cfg(games, synthetic=synthetic, callback=evaluator is not None, **cfg)
         self.games = games
@@ -62,6 +66,26 @@ class BatchedSearch:
         if evaluator is not None:
             self._eval_fn, self._pending = _eval_trampoline(evaluator)     # kept alive as long as the engine
             L.check(L.lib.az_search_set_evaluator(self._h, C.cast(self._eval_fn, C.c_void_p), None))
+        if tree_reuse:
+            self.set_tree_reuse(True)
+
+    def set_tree_reuse(self, on):
+        """az_search_set_tree_reuse: before the first set_roots() / SelfPlay.reset() only."""
+        L.check(L.lib.az_search_set_tree_reuse(self._h, int(on)))
+
+    @property
+    def tree_reuse(self):
+        """True if re-roots keep the played move's subtree."""
+        on = C.c_int()
+        L.check(L.lib.az_search_reuse_stats(self._h, C.byref(on), None, None, None))
+        return bool(on.value)
+
+    def reuse_stats(self):
+        """{reroots, carried_visits, carried_nodes}: re-roots that kept a subtree, the visits their new
+        roots held and the nodes kept, since creation or the last SelfPlay.reset()."""
+        r, v, n = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        L.check(L.lib.az_search_reuse_stats(self._h, None, C.byref(r), C.byref(v), C.byref(n)))
+        return {"reroots": r.value, "carried_visits": v.value, "carried_nodes": n.value}
 
     def __del__(self):
         try:
@@ -182,7 +206,8 @@ class MCTree:
 
     @classmethod
     def init(cls, model, state, apply_noise, **cfg):
-        """MCTree::init (tree.rs:37-64): evaluate the root with `model`."""
+        """MCTree::init (tree.rs:37-64): evaluate the root with `model`.  tree_reuse=True (in cfg):
+        traverse_new keeps the played move's subtree (BatchedSearch)."""
         s = BatchedSearch(model, games=1, **cfg)
         hist = list(state.history())
         s.set_roots([hist], apply_noise=apply_noise)

@@ -151,8 +151,11 @@ struct Counters {                  // device-side statistics
     int log_count;
     int log_prior_count;
     int overflow;
-    int pad[1];
+    int max_remain;                // tree reuse: the most simulations any root re-rooted by the last k_finish
+                                   // still needs (the host clears it before the launch and reads it after)
     unsigned long long shared;     // shared leaves of the leaf-parallel search (az_search_leaf_stats)
+    // tree reuse (az_search_reuse_stats): re-roots that kept a subtree, the visits and nodes they kept
+    unsigned long long reroots, carried_visits, carried_nodes;
 };
 
 // everything the tree kernels need, passed by value
@@ -198,6 +201,11 @@ struct Engine {
     // K = 1 is the layout above and runs the kernels above
     int K;
     int* leaf_src;                         // [G][K] LEAF_SHARED: the wave's leaf whose value this one takes
+    // tree reuse (az_search_set_tree_reuse): k_finish keeps the played move's subtree and a
+    // move's search tops the root up to S visits.  reuse = 0 is the search above, bit for bit
+    int reuse;
+    int* remap;                            // [G][NMAX] k_finish scratch: a node's id after the compaction, -1 = dropped
+    uint32_t* remap_eb;                    // [G][NMAX] ... and its edge_begin after it
 };
 
 // ---------------- network ----------------

@@ -22,6 +22,8 @@
 // re-roots on the child keeping its priors/edges but resetting N/W and dropping every
 // other node (traverse_new, tree.rs:239-256), then applies Dirichlet noise
 // (tree.rs:272-289).  Nothing crosses PCIe inside a move.
+// Opt-in tree reuse (az_search_set_tree_reuse): the re-root keeps the child's whole subtree,
+// compacted in place (reroot_keep_subtree), and a move's search tops the root up to S visits (budget_left).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -39,9 +41,20 @@
 
 namespace azi {
 
+// Tree reuse (Engine::reuse): a move's search tops the root up to S visits, so game g
+// (g < G) takes a leaf in a step only while its root holds fewer.  A step's select, expand and backup all
+// ask this of the same tree -- the root's nsum moves only in the backup, which asks before it adds -- so
+// the three agree on whether the game took a leaf.  Read as a vector load: the wave's own backup, or an
+// earlier launch, wrote it.  Always true with reuse off.
+__device__ __forceinline__ bool budget_left(const Engine& E, int g) {
+    if (!E.reuse) return true;
+    const Node* root = game_nodes(E, vgpr_index(g));
+    return load_fresh(reinterpret_cast<const int*>(&root->nsum)) < E.S;
+}
+
 __global__ void __launch_bounds__(256) k_select(Engine E) {
     const int g = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    if (g >= E.G || !E.active[g]) return;
+    if (g >= E.G || !E.active[g] || !budget_left(E, g)) return;
     select_game(E, g, threadIdx.x & 63);
 }
 
@@ -83,7 +96,7 @@ __global__ void __launch_bounds__(64) k_expand(Engine E, int step) {
     const int lane = threadIdx.x;
     const int g = vgpr_index(blockIdx.x);
     int nid = -1;
-    const int kind = expand_leaf_wave(E, g, lane, &nid);
+    const int kind = g < E.G && budget_left(E, g) ? expand_leaf_wave(E, g, lane, &nid) : X_NONE;
     if (lane == 0) {
         if (kind == X_ROW) {
             const int row = atomicAdd(step_rows(E, step), 1);
@@ -103,7 +116,7 @@ __global__ void __launch_bounds__(256) k_backup(Engine E, int step) {
     const int g = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const int lane = threadIdx.x & 63;
     if (g == 0 && lane == 0) backup_stats(E, step);
-    if (g >= E.G || !E.active[g]) return;
+    if (g >= E.G || !E.active[g] || !budget_left(E, g)) return;
     backup_game(E, g, lane);
 }
 
@@ -130,14 +143,15 @@ __global__ void __launch_bounds__(STEP_WPB * 64) k_step(Engine E, int step, int 
     const int g = blockIdx.x * STEP_WPB + w;
     __shared__ int s_kind[STEP_WPB], s_nid[STEP_WPB], s_base;
     ST_STAMP(0);
-    const bool live = g < E.G && E.active[g];
+    bool live = g < E.G && E.active[g];
     if (bstep >= 0) {
         if (blockIdx.x == 0 && threadIdx.x == 0) backup_stats(E, bstep);
-        if (live) backup_game(E, g, lane);
+        if (live && budget_left(E, g)) backup_game(E, g, lane);   // the game took a leaf in bstep
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     }
     ST_STAMP(1);
     int kind = X_NONE, nid = -1;
+    live = live && budget_left(E, g);                             // ... and takes one in this step
     if (live) {
         select_game(E, g, lane);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -298,6 +312,12 @@ __global__ void k_adopt_rows_done(Engine E) {
 // of S simulations holds at most S + 1 = NMAX - 1 nodes and 218 (NMAX - 1) edges of EMAX = 218 NMAX +
 // MAX_EDGES, so neither belongs to a node of any tree, live or inactive; an expansion that ever reached
 // them would write them before anything reads them.  node_count / edge_count are not touched.
+// With tree reuse the bound is the same one, so `overflow` stays 0 by construction there too: a root
+// carried with nsum = c visits has at most c + 1 nodes (the root, and one per simulation that went through
+// it, since each expands at most one node), the move then runs S - c simulations of at most one node each:
+// at most S + 1 nodes again, each of at most 218 edges, compacted to the front of both arenas.  (Adoption
+// rebuilds every live root from its history first -- k_root_setup, node_count = 1 -- so the staging below
+// never meets a carried tree.)
 __device__ __forceinline__ int template_node(const Engine& E) { return E.NMAX - 1; }
 __device__ __forceinline__ int template_edge0(const Engine& E) { return E.EMAX - MAX_EDGES; }
 
@@ -330,6 +350,124 @@ __global__ void __launch_bounds__(256) k_copy_start_template(Engine E) {
         atomicAdd(&E.ctr->evals, (unsigned long long)load_fresh(rows));
         *rows = 0;
     }
+}
+
+// ------------------------------------------------------------------ re-root with tree reuse
+// inclusive prefix sum over the wave (all lanes active)
+__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+// Engine::reuse: node `child` of game g becomes node 0 and its subtree is kept, compacted in place to the
+// front of the game's node and edge arenas by the game's one wavefront (no second arena).  What makes that
+// possible: the bump allocators of expand_leaf_wave hand out node ids and edge ranges together
+// (nid = node_count++, edge_begin = edge_count, edge_count += nedges), and a node is allocated after its
+// parent, so ids and edge_begins both ascend from parent to child and in step with each other.  Kept nodes
+// keep their order, so a node's new id and new edge_begin -- prefix sums over the kept nodes before it -- never
+// exceed the old ones, and moving ascending never overwrites a record still to be read.
+//   pass 1, 64 node ids a chunk from `child` up: membership (a node is kept iff its parent is; parents of an
+//     earlier chunk are looked up in the table, parents inside the chunk resolved over ballots), then wave
+//     prefix sums of 1 and of nedges over the kept lanes -> remap[old id] (-1: dropped), remap_eb[old id];
+//   pass 2, the same chunks again: every load of the chunk's node records, positions and table entries
+//     before any of its stores (parent, depth and edge_begin rewritten); then the chunk's kept nodes one at
+//     a time: all of the node's <= 4 x 64 edges and child_hdr words loaded, child ids and headers rewritten
+//     from the tables, then stored.  A node's destination ends at or before its source, and every later
+//     source lies beyond it.
+// P, W, N, idx (PROMO_FLAG included) and the markers CHILD_NONE / CHILD_DRAW / CHILD_WIN move unchanged.
+// The tables are per-game global scratch ([G][NMAX]: S is the caller's and need not fit LDS), written and
+// read by this wave alone: a workgroup-scope fence orders a chunk's stores before the next loads, and
+// the loads go through load_fresh.  *nk, *ek: nodes and edges kept; *dmax: the largest rebased depth.
+__device__ void reroot_keep_subtree(const Engine& E, int g, int lane, int child, int* nk_out, int* ek_out, int* dmax_out) {
+    Node* nodes = game_nodes(E, g);
+    Edge* edges = game_edges(E, g);
+    azc::Pos* npos = game_npos(E, g);
+    uint32_t* chdr = E.child_hdr + (size_t)g * E.EMAX;
+    int* remap = E.remap + (size_t)g * E.NMAX;
+    int* remap_eb = reinterpret_cast<int*>(E.remap_eb + (size_t)g * E.NMAX);
+    const int nc = min(E.node_count[g], E.NMAX);
+    const int d0 = nodes[child].depth;
+    int nk = 0, ek = 0, dmax = 0;
+    for (int base = child; base < nc; base += 64) {
+        const int i = base + lane;
+        const bool valid = i < nc;
+        const Node nd = nodes[valid ? i : child];
+        const int p = nd.parent;
+        bool known = true, keep = false;
+        if (valid) {
+            if (i == child) keep = true;
+            else if (p < child) keep = false;
+            else if (p < base) keep = load_fresh(&remap[p]) >= 0;
+            else known = false;                                // the parent is a lower lane of this chunk
+        }
+        for (;;) {                                             // the lowest unknown lane's parent is known
+            const unsigned long long km = __ballot(known), kp = __ballot(keep);
+            if (km == ~0ull) break;
+            if (!known && ((km >> (p - base)) & 1ull)) { known = true; keep = (kp >> (p - base)) & 1ull; }
+        }
+        const int n = keep ? (int)nd.nedges : 0;
+        const int in = wave_incl_scan(keep ? 1 : 0, lane), ie = wave_incl_scan(n, lane);
+        if (valid) {
+            remap[i] = keep ? nk + in - 1 : -1;
+            remap_eb[i] = ek + ie - n;
+        }
+        if (keep) dmax = max(dmax, (int)nd.depth - d0);
+        nk += __builtin_amdgcn_readlane(in, 63);
+        ek += __builtin_amdgcn_readlane(ie, 63);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    }
+    for (int o = 32; o > 0; o >>= 1) dmax = max(dmax, __shfl_xor(dmax, o, 64));
+    for (int base = child; base < nc; base += 64) {
+        const int i = base + lane;
+        const bool valid = i < nc;
+        const int ic = valid ? i : child;
+        const Node nd = nodes[ic];
+        const int ni = valid ? load_fresh(&remap[ic]) : -1;
+        const int neb = load_fresh(&remap_eb[ic]);
+        const bool keep = ni >= 0;
+        azc::Pos ps = npos[ic];
+        const int np = keep && i != child ? load_fresh(&remap[nd.parent]) : -1;
+        if (keep) {
+            Node o;
+            o.edge_begin = (uint32_t)neb; o.nedges = nd.nedges; o.depth = (uint16_t)((int)nd.depth - d0);
+            o.nsum = nd.nsum; o.parent = np;
+            nodes[ni] = o;
+            npos[ni] = ps;
+        }
+        unsigned long long km = __ballot(keep);
+        while (km) {
+            const int l = (int)__builtin_ctzll(km);
+            km &= km - 1ull;
+            const int ob = __builtin_amdgcn_readlane((int)nd.edge_begin, l), n = __builtin_amdgcn_readlane((int)nd.nedges, l);
+            const int nb = __builtin_amdgcn_readlane(neb, l);
+            Edge ed[4];
+            uint32_t hd[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int e = max(min(lane + 64 * j, n - 1), 0);   // clamped: unconditional loads
+                ed[j] = edges[ob + e];
+                hd[j] = chdr[ob + e];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int c = ed[j].child;
+                if (lane + 64 * j < n && c >= 0) {
+                    ed[j].child = load_fresh(&remap[c]);
+                    hd[j] = (uint32_t)load_fresh(&remap_eb[c]) << 8 | (hd[j] & 255u);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int e = lane + 64 * j;
+                if (e < n) { edges[nb + e] = ed[j]; chdr[nb + e] = hd[j]; }
+            }
+        }
+    }
+    *nk_out = nk; *ek_out = ek; *dmax_out = dmax;
 }
 
 // ------------------------------------------------------------------ move step
@@ -428,6 +566,29 @@ __global__ void __launch_bounds__(64) k_finish(Engine E, int mode, const int* ac
     __syncthreads();
     const int ea = si[2];
     const int child = ea >= 0 ? edges[ea].child : CHILD_NONE;
+    if (child >= 0 && E.reuse) {
+        // tree reuse: the child's subtree stays, visits and scores as they are; the next move's search runs
+        // S - nsum >= 1 simulations on it (nsum <= N(edge) - 1: the visit that made the child is not in it)
+        const azc::Pos cp = npos[child];
+        const int carried = (int)nodes[child].nsum;
+        int nk, ek, dmax;
+        reroot_keep_subtree(E, g, lane, child, &nk, &ek, &dmax);
+        if (lane == 0) {
+            if (hl < HMAX) { hist[hl] = cp; E.hist_len[g] = hl + 1; }
+            E.ply[g] = ply + 1;
+            E.node_count[g] = nk;
+            E.edge_count[g] = ek;
+            E.max_depth[g] = dmax;
+            if (results) results[g] = azc::ONGOING;
+            atomicMax(&E.ctr->max_remain, E.S - carried);
+            atomicAdd(&E.ctr->reroots, 1ull);
+            atomicAdd(&E.ctr->carried_visits, (unsigned long long)carried);
+            atomicAdd(&E.ctr->carried_nodes, (unsigned long long)nk);
+        }
+        __syncthreads();
+        if (apply_noise) root_noise(E, g, gid, ply + 1, gam, kpos, sh);
+        return;
+    }
     if (child >= 0) {
         const azc::Pos cp = npos[child];
         const Node cn = nodes[child];
@@ -499,6 +660,7 @@ __global__ void __launch_bounds__(64) k_finish(Engine E, int mode, const int* ac
         E.node_count[g] = 1;
         E.edge_count[g] = sn;
         E.max_depth[g] = 0;
+        if (E.reuse) atomicMax(&E.ctr->max_remain, E.S);       // a fresh root: the whole search
     }
     __syncthreads();
     if (E.noise) root_noise(E, g, ngid, 0, gam, kpos, sh);
@@ -597,6 +759,9 @@ struct az_search {
     size_t finished_read = 0;
     bool roots_fresh = false;        // trees sized for exactly S sims per root
     int sim_cursor = 0;              // simulation steps of the current self-play move already run
+    bool roots_ever_set = false;     // az_search_set_tree_reuse must come before the first roots
+    int move_steps = 0;              // tree reuse: simulation steps of the current move = the most simulations any
+                                     // active root still needs (S after fresh roots, Counters::max_remain after a re-root)
     int64_t net_gen = 0;             // the net's generation (az_net_update*) when the roots were last set
     // timing
     bool timing = false;
@@ -761,6 +926,7 @@ int eval_rows(az_search* s) {
 // the chip in one round (auto), never with the FEN cache (its inserts are a separate kernel)
 bool use_persistent(const az_search* s) {
     if (s->E.K > 1) return false;      // one leaf per step only
+    if (s->E.reuse) return false;      // tree reuse: per-game simulation counts (a follow-up for k_sims32w)
     if (s->persist == 0 || s->E.cache_mask >= 0 || s->cfg.evaluator != AZ_EVAL_NET) return false;
     const NetDev* n = s->net->dev;
     if (!n->fused || !sims_persistent_supported(n)) return false;
@@ -862,8 +1028,7 @@ int run_sims_leaves(az_search* s, int i0, int i1) {
 
 // simulation steps [i0, i1) of the current move (run_sims(s) = the whole move)
 int run_sims(az_search* s, int i0 = 0, int i1 = -1) {
-    const int S = s->E.S;
-    if (i1 < 0) i1 = S;
+    if (i1 < 0) i1 = s->E.reuse ? s->move_steps : s->E.S;
     if (s->E.K > 1) return run_sims_leaves(s, i0, i1);
     const bool tm = s->timing;
     if (tm && ensure_step_events(s)) return -1;
@@ -968,6 +1133,8 @@ int upload_histories(az_search* s, const az_pos* start, const int32_t* hist, con
 int setup_roots(az_search* s, int apply_noise, bool save_template) {
     Engine& E = s->E;
     s->sim_cursor = 0;                 // new roots abandon any self-play move in progress
+    s->roots_ever_set = true;
+    s->move_steps = E.S;               // fresh roots carry nothing
     AZ_HIP(hipMemsetAsync(E.ctr->batch_count, 0, sizeof(E.ctr->batch_count), s->st));
     k_root_setup<<<(E.G + 63) / 64, 64, 0, s->st>>>(E);
     int rc = eval_rows(s);
@@ -1011,6 +1178,7 @@ int adopt_weights(az_search* s, int apply_noise, const char* who) {
     AZ_HIP(hipStreamSynchronize(s->st));
     if (s->net) s->net_gen = s->net->dev->generation;
     s->roots_fresh = true;
+    s->move_steps = E.S;               // tree reuse: the carried subtrees held the old net's evaluations
     return 0;
 }
 
@@ -1018,6 +1186,7 @@ int drain_records(az_search* s) {
     Counters c;
     AZ_HIP(hipMemcpyAsync(&c, s->E.ctr, sizeof(Counters), hipMemcpyDeviceToHost, s->st));
     AZ_HIP(hipStreamSynchronize(s->st));
+    if (s->E.reuse) s->move_steps = std::min(std::max(c.max_remain, 0), s->E.S);   // published by k_finish
     int nrec = std::min(c.rec_count, s->E.rec_cap);
     if (c.rec_count > s->E.rec_cap) return fail("step record buffer overflow");
     if (nrec == 0) return 0;
@@ -1262,11 +1431,17 @@ int az_search_advance(az_search* s, const int32_t* actions, int apply_noise, int
     std::vector<int> init(G, azc::ILLEGAL);
     AZ_HIP(hipMemcpy(dr, init.data(), G * 4, hipMemcpyHostToDevice));
     AZ_HIP(hipMemcpy(da, actions, G * 4, hipMemcpyHostToDevice));
+    if (s->E.reuse) AZ_HIP(hipMemsetAsync(&s->E.ctr->max_remain, 0, sizeof(int), s->st));
     k_finish<<<G, 64, 0, s->st>>>(s->E, 1, da, dr, apply_noise);
     AZ_HIP(hipGetLastError());
     AZ_HIP(hipStreamSynchronize(s->st));
     std::vector<int> res(G);
     AZ_HIP(hipMemcpy(res.data(), dr, G * 4, hipMemcpyDeviceToHost));
+    if (s->E.reuse) {                  // the steps of the next az_search_run: the most any re-rooted game needs
+        int mr = 0;
+        AZ_HIP(hipMemcpy(&mr, &s->E.ctr->max_remain, sizeof(int), hipMemcpyDeviceToHost));
+        s->move_steps = std::min(std::max(mr, 0), s->E.S);
+    }
     (void)hipFree(da); (void)hipFree(dr);
     s->roots_fresh = true;
     s->sim_cursor = 0;                 // re-rooted: a self-play move in progress is abandoned
@@ -1300,17 +1475,21 @@ static int selfplay_sims(az_search* s, int nsims, int* finished, int* active, in
     AZ_HIP(hipSetDevice(s->device));
     unsigned long long before = 0;
     AZ_HIP(hipMemcpy(&before, &s->E.ctr->games_finished, 8, hipMemcpyDeviceToHost));
-    const int i0 = s->sim_cursor, i1 = std::min(s->E.S, i0 + nsims);
+    // steps of this move: S, or with tree reuse the most simulations any active root still needs -- the
+    // move is done when every active root holds S visits
+    const int M = s->E.reuse ? s->move_steps : s->E.S;
+    const int i0 = s->sim_cursor, i1 = std::min(M, i0 + nsims);
     int rc = run_sims(s, i0, i1);
     if (rc) return rc;
     s->sim_cursor = i1;
-    if (move_done) *move_done = i1 == s->E.S;
-    if (i1 < s->E.S) {                 // the move is not complete: no action yet
+    if (move_done) *move_done = i1 == M;
+    if (i1 < M) {                      // the move is not complete: no action yet
         if (finished) *finished = 0;
         if (active) *active = -1;
         return 0;
     }
     s->sim_cursor = 0;
+    if (s->E.reuse) AZ_HIP(hipMemsetAsync(&s->E.ctr->max_remain, 0, sizeof(int), s->st));
     k_finish<<<s->E.G, 64, 0, s->st>>>(s->E, 0, nullptr, nullptr, s->cfg.noise);
     AZ_HIP(hipGetLastError());
     rc = drain_records(s);
@@ -1392,6 +1571,39 @@ int az_selfplay_drain(az_search* s, az_episode_step* out, int cap) {
 }
 
 int az_search_persistent(az_search* s) { return s && use_persistent(s) ? 1 : 0; }
+
+int az_search_set_tree_reuse(az_search* s, int on) {
+    if (!s) return fail("null search");
+    if (on != 0 && on != 1) return fail("az_search_set_tree_reuse: on must be 0 or 1, not " + std::to_string(on));
+    if (s->roots_ever_set)
+        return fail("az_search_set_tree_reuse: must precede the first az_search_set_roots* / az_selfplay_reset");
+    if (on && s->E.K > 1)
+        return fail("az_search_set_tree_reuse: tree reuse and leaves > 1 (cfg.leaves = " + std::to_string(s->E.K) +
+                    ") do not combine yet");
+    if (on && !s->E.remap) {
+        AZ_HIP(hipSetDevice(s->device));
+        int rc = dalloc(s, &s->E.remap, (size_t)s->E.G * s->E.NMAX);
+        rc |= dalloc(s, &s->E.remap_eb, (size_t)s->E.G * s->E.NMAX);
+        if (rc) return -1;
+    }
+    s->E.reuse = on;
+    return 0;
+}
+
+int az_search_reuse_stats(az_search* s, int* on, uint64_t* reroots, uint64_t* carried_visits, uint64_t* carried_nodes) {
+    if (!s) return fail("null search");
+    if (on) *on = s->E.reuse;
+    if (reroots || carried_visits || carried_nodes) {
+        AZ_HIP(hipSetDevice(s->device));
+        AZ_HIP(hipStreamSynchronize(s->st));
+        Counters c;
+        AZ_HIP(hipMemcpy(&c, s->E.ctr, sizeof(c), hipMemcpyDeviceToHost));
+        if (reroots) *reroots = (uint64_t)c.reroots;
+        if (carried_visits) *carried_visits = (uint64_t)c.carried_visits;
+        if (carried_nodes) *carried_nodes = (uint64_t)c.carried_nodes;
+    }
+    return 0;
+}
 
 int az_search_leaf_stats(az_search* s, int* leaves, uint64_t* shared_leaves) {
     if (!s) return fail("null search");
@@ -1525,6 +1737,8 @@ int azi::search_set_roots_device(az_search* s) {
     Engine& E = s->E;
     s->sim_cursor = 0;
     s->roots_fresh = false;
+    s->roots_ever_set = true;
+    s->move_steps = E.S;
     AZ_HIP(hipMemsetAsync(E.ctr->batch_count, 0, sizeof(E.ctr->batch_count), s->st));
     k_root_setup<<<(E.G + 63) / 64, 64, 0, s->st>>>(E);
     int rc = eval_rows(s);

@@ -348,8 +348,37 @@ int az_search_persistent(az_search* s);
  * may be NULL.  Beside az_search_stats: sims == evals + cache_hits + terminal_leaves + shared_leaves + the
  * simulations whose selection ended on an edge already known to end the game -- terminal_leaves counts an
  * ended game once, when an expansion finds it, at every K; the later visits of that edge are in `sims`
- * only.  az_search_persistent is 0 at K > 1. */
+ * only.  az_search_persistent is 0 at K > 1.  With tree reuse (az_search_set_tree_reuse) the identity
+ * holds as it stands: `sims` counts the simulations run (backed up), not cfg.sims per move -- a move on a
+ * root that carried c visits runs cfg.sims - c -- and the carried visits are in no counter but
+ * az_search_reuse_stats' carried_visits. */
 int az_search_leaf_stats(az_search* s, int* leaves, uint64_t* shared_leaves);
+
+/* Tree reuse (opt-in; off: every re-root starts from an empty tree, the reference's traverse_new,
+ * tree.rs:239-256, bit for bit).  With on = 1 a re-root on a played move that has a child node -- in
+ * az_selfplay_step / az_selfplay_run_sims and in az_search_advance -- keeps that child's subtree: the child
+ * becomes the root with its edges' priors, scores, visits and children as they are, every node below it
+ * stays, everything else is dropped, depths are rebased (the root's is 0, the reported search depth is the
+ * largest rebased depth kept).  Root noise (apply_noise) goes onto the kept priors from the same stream
+ * (seed, game id, ply, 0).  A move's search then tops the root up: game g runs cfg.sims - (the root's
+ * visits) >= 1 simulations, so its root's visits sum to exactly cfg.sims when the move ends, and the
+ * improved policy, the move choice and the EpisodeStep come from those visits as before.  az_search_run
+ * likewise runs cfg.sims - visits per game, none for a root already there.  A call runs as many simulation
+ * steps as the neediest active game asks; a game that is done takes no leaf, writes no row and moves no
+ * counter.  az_selfplay_run_sims sets *move_done when every active root holds cfg.sims visits.  Fresh roots
+ * (az_search_set_roots*, az_selfplay_reset, a restarted continuous slot) carry nothing, and az_*_adopt_net
+ * discards the carried subtrees: they hold the old weights' evaluations.  The results are a DIFFERENT
+ * search from the reference's (its playing strength is not measured); what they are is restated in
+ * tests/treereuse_ref.py, which the engine equals bit for bit.
+ * Must precede the first az_search_set_roots* / az_selfplay_reset (like az_search_set_evaluator); later,
+ * with `on` outside 0 / 1, or with on = 1 on a handle of cfg.leaves > 1, it is an error and nothing
+ * changes.  With reuse on az_search_persistent is 0.  The arena's and the tournament's MCTS players keep a
+ * fresh tree per ply. */
+int az_search_set_tree_reuse(az_search* s, int on);
+/* *on = the mode; *reroots = re-roots that kept a subtree, *carried_visits = the sum over them of the new
+ * root's visits, *carried_nodes = the sum of the nodes kept (the new root included) -- counted like
+ * az_search_stats, since creation or the last az_selfplay_reset.  Any pointer may be NULL. */
+int az_search_reuse_stats(az_search* s, int* on, uint64_t* reroots, uint64_t* carried_visits, uint64_t* carried_nodes);
 
 /* Evaluation log (cfg.record_evals): keys[n] (fen keys), values[n], CSR priors at the
  * legal move indices. Pass NULL arrays to query sizes. */
