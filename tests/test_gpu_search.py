@@ -163,15 +163,28 @@ def test_fen_cache_search_bit_exact(require_gpu):
 def test_search_survives_nan_network(require_gpu):
     """A diverged network (NaN everywhere) must not take the engine out of bounds: every PUCT
     value is NaN, nothing beats -inf, and the walk takes the first edge (the reference keeps
-    its initial index, tree.rs:121-131).  The search completes with every simulation counted."""
+    its initial index, tree.rs:121-131).  The search completes with every simulation counted, and its
+    visits, improved policy and depth are those of the numpy restatement (tests/leafpar_ref.py, whose pick
+    restates "takes the first edge") replaying the handle's own all-NaN rows from the eval log."""
+    import leafpar_ref as R
+    from test_gpu_leafpar import log_evaluator
     w = A.random_weights(2, 32, seed=5)
     w[:] = np.nan
     net = A.AlphaZero(2, 32, weights=w, dtype="bf16")
-    s = A.BatchedSearch(net, games=4, sims=64, seed=1)
-    s.set_roots([[], [588], [], [588]], apply_noise=True)
+    hs = [[], [588], [], [588]]
+    s = A.BatchedSearch(net, games=4, sims=64, seed=1, record_evals=True, eval_log_cap=4096)
+    s.set_roots(hs, apply_noise=True)
     imp, vis, dep = s.run()
     assert np.all(vis.sum(axis=1) == 64)
     assert np.all((dep >= 1) & (dep <= 64))
+    keys, vals, off, idx, pri = s.eval_log()
+    assert len(keys) > 4 and np.isnan(vals).all() and np.isnan(pri).all()
+    ev = log_evaluator(s)
+    for g, h in enumerate(hs):
+        rv, ri, rd, _, _ = R.search(None, h, (64, 1), ev, O.lib().ref_stream_key(1, g, len(h), 0))
+        assert np.array_equal(vis[g].astype(np.float32), rv), g
+        assert np.array_equal(imp[g].view(np.uint32), ri.view(np.uint32)), g
+        assert dep[g] == rd, g
 
 
 @pytest.mark.parametrize("cache", [0, 1 << 16])
