@@ -85,6 +85,28 @@ class AzPlayerSearch(C.Structure):
 
 PLAYER_MCTS, PLAYER_BASE, PLAYER_MINIMAX, PLAYER_RANDOM, PLAYER_EXTERNAL = 0, 1, 2, 3, 4
 
+
+class AzTreeNode(C.Structure):
+    """az_tree_node: one node of az_search_read_tree's export (24 B)."""
+    _fields_ = [("parent", C.c_int32), ("parent_edge", C.c_int32), ("edge_begin", C.c_int32), ("nedges", C.c_int32),
+                ("depth", C.c_int32), ("nsum", C.c_uint32)]
+
+
+class AzTreeEdge(C.Structure):
+    """az_tree_edge: one edge of az_search_read_tree's export (24 B)."""
+    _fields_ = [("prior", C.c_float), ("score", C.c_float), ("visits", C.c_uint32), ("index", C.c_int32),
+                ("child", C.c_int32), ("flags", C.c_uint32)]
+
+
+# the same records as numpy dtypes (the arrays BatchedSearch.read_tree hands to tree_views)
+TREE_NODE_DTYPE = np.dtype([("parent", "<i4"), ("parent_edge", "<i4"), ("edge_begin", "<i4"), ("nedges", "<i4"),
+                            ("depth", "<i4"), ("nsum", "<u4")])
+TREE_EDGE_DTYPE = np.dtype([("prior", "<f4"), ("score", "<f4"), ("visits", "<u4"), ("index", "<i4"),
+                            ("child", "<i4"), ("flags", "<u4")])
+# az_tree_edge.child where it is no node ordinal (include/az.h AZ_TREE_*)
+TREE_UNEXPANDED, TREE_DRAW, TREE_WIN, TREE_CUT = -1, -2, -3, -4
+TREE_EDGE_PROMO = 1     # az_tree_edge.flags bit 0
+
 # az_eval_fn (include/az.h): int (*)(void* ctx, const az_pos*, int n, float* policy, float* value)
 EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(AzPos), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float))
 
@@ -145,6 +167,9 @@ SIGNATURES = [
                                            P(C.c_int32), C.c_int]),
     ("az_search_run", C.c_int, [C.c_void_p, P(C.c_float), P(C.c_uint32), P(C.c_int32)]),
     ("az_search_read_roots", C.c_int, [C.c_void_p, P(C.c_float), P(C.c_uint32), P(C.c_int32)]),
+    ("az_search_read_tree", C.c_int, [C.c_void_p, P(C.c_int32), C.c_int, C.c_int, C.c_int, P(C.c_int64), P(C.c_int64),
+                                      P(AzTreeNode), C.c_int64, P(AzTreeEdge), C.c_int64, P(AzPos)]),
+    ("az_search_read_pv", C.c_int, [C.c_void_p, P(C.c_int32), C.c_int, P(C.c_int32), P(C.c_float), P(C.c_uint32)]),
     ("az_search_advance", C.c_int, [C.c_void_p, P(C.c_int32), C.c_int, P(C.c_int32)]),
     ("az_selfplay_reset", C.c_int, [C.c_void_p]),
     ("az_selfplay_step", C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int)]),

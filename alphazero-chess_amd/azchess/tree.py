@@ -44,6 +44,107 @@ def _eval_trampoline(evaluator):
     return L.EVAL_FN(fn), pending
 
 
+class TreeView:
+    """One node of an exported search tree (BatchedSearch.read_tree) with the reference's field names
+    (MCTree, tree.rs:25-34): a light view over one game's numpy record arrays (L.TREE_NODE_DTYPE,
+    L.TREE_EDGE_DTYPE, L.POS_DTYPE), rooted at node `ordinal`.  Nothing is copied until a field is read."""
+
+    __slots__ = ("_nodes", "_edges", "_states", "ordinal")
+
+    def __init__(self, nodes, edges, states=None, ordinal=0):
+        self._nodes, self._edges, self._states, self.ordinal = nodes, edges, states, int(ordinal)
+
+    @property
+    def record(self):
+        """the node's az_tree_node record"""
+        return self._nodes[self.ordinal]
+
+    @property
+    def edges(self):
+        """the node's az_tree_edge records, in the order the selection scans them"""
+        r = self._nodes[self.ordinal]
+        return self._edges[int(r["edge_begin"]):int(r["edge_begin"]) + int(r["nedges"])]
+
+    @property
+    def moves(self):
+        """legal move indices in legal_moves() order of first appearance, a promotion's index four times
+        (tree.rs:86-89)"""
+        e = self.edges
+        return np.repeat(e["index"], np.where(e["flags"] & L.TREE_EDGE_PROMO, 4, 1)).astype(np.int32)
+
+    def _dense(self, field):
+        e = self.edges
+        out = np.zeros(L.ACTION_SPACE, np.float32)
+        out[e["index"]] = e[field]
+        return out
+
+    @property
+    def policy(self):
+        """dense [4096] f32 priors (noised at a noised root)"""
+        return self._dense("prior")
+
+    @property
+    def visits(self):
+        return self._dense("visits")
+
+    @property
+    def scores(self):
+        return self._dense("score")
+
+    @property
+    def nodes(self):
+        """move index -> child TreeView, for the edges whose child node is in the export"""
+        return {int(e["index"]): TreeView(self._nodes, self._edges, self._states, e["child"])
+                for e in self.edges if e["child"] >= 0}
+
+    @property
+    def terminal(self):
+        """move index -> "draw" / "win" for the moves known to end the game"""
+        return {int(e["index"]): "draw" if e["child"] == L.TREE_DRAW else "win"
+                for e in self.edges if e["child"] in (L.TREE_DRAW, L.TREE_WIN)}
+
+    @property
+    def cut(self):
+        """move indices whose child node min_visits / max_depth left out of the export"""
+        return [int(e["index"]) for e in self.edges if e["child"] == L.TREE_CUT]
+
+    @property
+    def state(self):
+        """the node's Position (read_tree(states=True))"""
+        if self._states is None:
+            raise ValueError("the tree was read without states (read_tree(states=True))")
+        from .chess import array_position
+        return array_position(self._states, self.ordinal)
+
+    @property
+    def depth(self):
+        return int(self._nodes[self.ordinal]["depth"])
+
+    @property
+    def nsum(self):
+        """visits summed over the node's edges"""
+        return int(self._nodes[self.ordinal]["nsum"])
+
+    def max_subtree_depth(self):
+        """the deepest exported node below this one, in plies from it (tree.rs:258-269)"""
+        n = self._nodes
+        below = np.zeros(len(n), bool)
+        below[self.ordinal] = True
+        for i in range(self.ordinal + 1, len(n)):        # parents precede their children
+            below[i] = below[n["parent"][i]]
+        return int(n["depth"][below].max()) - self.depth
+
+
+def tree_views(node_off, edge_off, nodes, edges, states=None):
+    """The root TreeView of every game of an az_search_read_tree export (CSR offsets and record arrays; a pure
+    host function)."""
+    out = []
+    for k in range(len(node_off) - 1):
+        n0, n1, e0, e1 = int(node_off[k]), int(node_off[k + 1]), int(edge_off[k]), int(edge_off[k + 1])
+        out.append(TreeView(nodes[n0:n1], edges[e0:e1], None if states is None else states[n0:n1]))
+    return out
+
+
 class BatchedSearch:
     """G concurrent game trees on one device."""
 
@@ -137,6 +238,49 @@ class BatchedSearch:
         L.check(L.lib.az_search_read_roots(self._h, L.fptr(imp), L.u32ptr(vis), L.i32ptr(dep)))
         return imp, vis, dep
 
+    def read_tree_arrays(self, games=None, min_visits=0, max_depth=None, states=False):
+        """az_search_read_tree -> (node_off, edge_off, nodes, edges, states or None): the CSR export of the
+        listed slots' trees (None: all), sized by a first call and filled by a second."""
+        if games is None:
+            gl, n = None, self.games
+        else:
+            gl = np.ascontiguousarray(games, np.int32)
+            n = len(gl)
+        gp = None if gl is None else L.i32ptr(gl)
+        md = -1 if max_depth is None else int(max_depth)
+        noff, eoff = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        L.check(L.lib.az_search_read_tree(self._h, gp, n, int(min_visits), md, i64(noff), i64(eoff), None, 0, None, 0,
+                                          None))
+        nodes = np.zeros(max(int(noff[n]), 1), L.TREE_NODE_DTYPE)
+        edges = np.zeros(max(int(eoff[n]), 1), L.TREE_EDGE_DTYPE)
+        pos = np.zeros(max(int(noff[n]), 1), L.POS_DTYPE) if states else None
+        L.check(L.lib.az_search_read_tree(
+            self._h, gp, n, int(min_visits), md, i64(noff), i64(eoff),
+            nodes.ctypes.data_as(C.POINTER(L.AzTreeNode)), len(nodes), edges.ctypes.data_as(C.POINTER(L.AzTreeEdge)),
+            len(edges), pos.ctypes.data_as(C.POINTER(L.AzPos)) if states else None))
+        return noff, eoff, nodes[:int(noff[n])], edges[:int(eoff[n])], pos[:int(noff[n])] if states else None
+
+    def read_tree(self, games=None, min_visits=0, max_depth=None, states=False):
+        """The search trees of the listed slots (None: all) as they stand, read from the device: a list of
+        root TreeViews with the reference's MCTree fields at every node.  A child node is exported only if
+        its edge has visits >= min_visits and its depth is <= max_depth (None: no limit; 0: the roots alone);
+        where that leaves an existing child out the move is listed in TreeView.cut.  states=True also
+        brings every node's Position.  Callable wherever read_roots() is; reading changes nothing."""
+        return tree_views(*self.read_tree_arrays(games, min_visits, max_depth, states))
+
+    def read_pv(self, cap=64):
+        """The principal variation of every game -> (list of move-index lists, q [G] f32, visits [G] u32):
+        from the root the most visited move (ties to the larger index, self-play's rule), down while it has
+        a child node, at most `cap` moves; q and visits are the first move's score / visits and visits."""
+        moves = np.zeros((self.games, max(cap, 1)), np.int32)
+        ln = np.zeros(self.games, np.int32)
+        q = np.zeros(self.games, np.float32)
+        vis = np.zeros(self.games, np.uint32)
+        L.check(L.lib.az_search_read_pv(self._h, L.i32ptr(moves) if cap > 0 else None, int(cap), L.i32ptr(ln), L.fptr(q),
+                                        L.u32ptr(vis)))
+        return [moves[g, :ln[g]].tolist() for g in range(self.games)], q, vis
+
     def advance(self, actions, apply_noise=True):
         a = np.ascontiguousarray(actions, np.int32)
         res = np.zeros(self.games, np.int32)
@@ -216,8 +360,20 @@ class MCTree:
     def monte_carlo_tree_search(self):
         """tree.rs:106-115: run the simulations, return the improved policy [4096]."""
         imp, vis, dep = self._s.run()
-        self.visits, self.depth = vis[0].astype(np.float32), int(dep[0])
+        self.depth = int(dep[0])
         return imp[0]
+
+    def view(self, states=True):
+        """the tree as it stands on the device: its root TreeView (BatchedSearch.read_tree)"""
+        return self._s.read_tree(games=[0], states=states)[0]
+
+    # the reference's public fields (tree.rs:25-34), read from the device on access
+    nodes = property(lambda self: self.view().nodes, doc="move index -> child TreeView")
+    moves = property(lambda self: self.view(False).moves, doc="legal move indices, promotions four times")
+    policy = property(lambda self: self.view(False).policy, doc="dense [4096] f32 priors")
+    visits = property(lambda self: self.view(False).visits, doc="dense [4096] f32 visits")
+    scores = property(lambda self: self.view(False).scores, doc="dense [4096] f32 scores")
+    state = property(lambda self: self.view().state, doc="the root's Position")
 
     def max_subtree_depth(self):
         return self.depth

@@ -208,6 +208,18 @@ struct Engine {
     uint32_t* remap_eb;                    // [G][NMAX] ... and its edge_begin after it
 };
 
+// ---------------- tree read-out (tree_read.hip: az_search_read_tree / az_search_read_pv) ----------------
+static_assert(sizeof(az_tree_node) == 24 && sizeof(az_tree_edge) == 24, "tree export record layout");
+static_assert(AZ_TREE_UNEXPANDED == CHILD_NONE && AZ_TREE_DRAW == CHILD_DRAW && AZ_TREE_WIN == CHILD_WIN,
+              "the export's edge markers are the engine's");
+struct TreeRead;          // a search's read-out scratch (device), made by its first tree_read
+void tree_read_free(TreeRead* t);
+// the work of az_search_read_tree on the trees of E, ordered after what `st` holds; complete on return
+int tree_read(const Engine& E, hipStream_t st, TreeRead** scratch, const int32_t* games, int n, int min_visits,
+              int max_depth, int64_t* node_off, int64_t* edge_off, az_tree_node* nodes, int64_t node_cap,
+              az_tree_edge* edges, int64_t edge_cap, az_pos* states);
+int tree_read_pv(const Engine& E, hipStream_t st, int32_t* moves, int cap, int32_t* len, float* q, uint32_t* visits);
+
 // ---------------- network ----------------
 struct NetDev {
     int blocks = 0, filters = 0, dtype = 0, device = 0;

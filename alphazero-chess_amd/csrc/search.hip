@@ -763,6 +763,7 @@ struct az_search {
     int move_steps = 0;              // tree reuse: simulation steps of the current move = the most simulations any
                                      // active root still needs (S after fresh roots, Counters::max_remain after a re-root)
     int64_t net_gen = 0;             // the net's generation (az_net_update*) when the roots were last set
+    TreeRead* tree = nullptr;        // scratch of az_search_read_tree (tree_read.hip), made by its first call
     // timing
     bool timing = false;
     bool fused_steps = AZ_FUSED_STEPS != 0;   // k_step (backup + select + expand in one launch); env AZ_FUSED_STEPS=0: separate kernels
@@ -1354,6 +1355,7 @@ int az_search_destroy(az_search* s) {
     (void)hipSetDevice(s->device);
     if (s->st) (void)hipStreamSynchronize(s->st);
     for (void* p : s->allocs) (void)hipFree(p);
+    tree_read_free(s->tree);
     for (void* p : {(void*)s->h_pos, (void*)s->h_pol, (void*)s->h_val})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
@@ -1418,6 +1420,24 @@ int az_search_read_roots(az_search* s, float* improved, uint32_t* visits, int32_
     if (!s) return fail("null search");
     AZ_HIP(hipSetDevice(s->device));
     return read_roots(s, improved, visits, depth);
+}
+
+// Whole trees and principal variations (tree_read.hip).  Like read_roots they run on the search's stream
+// behind whatever it holds; run_sims never returns with a backup still to launch, so the tree they see is
+// the tree after the simulations run so far.
+int az_search_read_tree(az_search* s, const int32_t* games, int n, int min_visits, int max_depth, int64_t* node_off,
+                        int64_t* edge_off, az_tree_node* nodes, int64_t node_cap, az_tree_edge* edges, int64_t edge_cap,
+                        az_pos* states) {
+    if (!s) return fail("null search");
+    AZ_HIP(hipSetDevice(s->device));
+    return tree_read(s->E, s->st, &s->tree, games, n, min_visits, max_depth, node_off, edge_off, nodes, node_cap,
+                     edges, edge_cap, states);
+}
+
+int az_search_read_pv(az_search* s, int32_t* moves, int cap, int32_t* len, float* q, uint32_t* visits) {
+    if (!s) return fail("null search");
+    AZ_HIP(hipSetDevice(s->device));
+    return tree_read_pv(s->E, s->st, moves, cap, len, q, visits);
 }
 
 int az_search_advance(az_search* s, const int32_t* actions, int apply_noise, int32_t* result) {

@@ -246,6 +246,66 @@ int az_search_run(az_search* s, float* improved, uint32_t* visits, int32_t* dept
  * visits all 0 and depth 0; its improved policy is 0 / 0: NaN at the indices of the root's legal
  * moves and 0 everywhere else (bench.py --dump-outputs reads the roots' legal moves off it). */
 int az_search_read_roots(az_search* s, float* improved, uint32_t* visits, int32_t* depth);
+
+/* Whole search trees, read from the device: the reference's public MCTree (tree.rs:25-34: nodes, moves, state,
+ * policy, visits, scores at every node) as compact CSR records.
+ * az_tree_edge.child is the child node's ordinal within its game, or one of: */
+enum {
+    AZ_TREE_UNEXPANDED = -1,   /* no simulation has taken the move yet */
+    AZ_TREE_DRAW = -2,         /* the move ends the game in a draw */
+    AZ_TREE_WIN = -3,          /* the move wins the game for the side that plays it */
+    AZ_TREE_CUT = -4           /* the move has a child node that min_visits / max_depth left out */
+};
+typedef struct {
+    int32_t parent;            /* ordinal of the parent node within the game, -1 at the root */
+    int32_t parent_edge;       /* which of the parent's edges leads here (0 .. parent.nedges - 1), -1 at the root */
+    int32_t edge_begin;        /* the node's edges: [edge_begin, edge_begin + nedges) of the game's edges */
+    int32_t nedges;
+    int32_t depth;             /* root = 0 */
+    uint32_t nsum;             /* visits summed over the node's edges */
+} az_tree_node;                /* 24 B */
+typedef struct {
+    float prior;               /* policy[index] (with the Dirichlet noise at a noised root) */
+    float score;               /* scores[index]: the backed-up values' sum; Q = score / visits */
+    uint32_t visits;           /* visits[index] */
+    int32_t index;             /* the move index, 0..4095 */
+    int32_t child;             /* ordinal of the child node within the game, or AZ_TREE_* */
+    uint32_t flags;            /* bit 0: the index stands for the four promotion entries of `moves` */
+} az_tree_edge;                /* 24 B */
+/* The trees of the n slots listed in `games` (NULL: all cfg.games slots in slot order, n is ignored; a slot
+ * may repeat and is then exported once per mention).  CSR: game k's nodes are nodes[node_off[k] ..
+ * node_off[k+1]) and its edges edges[edge_off[k] .. edge_off[k+1]); node_off and edge_off have n + 1
+ * entries; parent, edge_begin and child are relative to the game's own ranges.  Node 0 is the root.  Nodes
+ * come in ascending engine id -- creation order, the order the tree-reuse compaction keeps -- so every
+ * node's parent has a smaller ordinal.  A node's edges are all of its edges in the order the selection scans
+ * them: the distinct move indices by first appearance in legal_moves() order.  states (may be NULL): one
+ * az_pos per exported node, in node order, flags and rep_key as the engine holds them.
+ * Pruning: a child node is exported only if its parent is, its edge has visits >= min_visits and its depth
+ * is <= max_depth (max_depth < 0: no limit).  An edge whose existing child node was left out reads
+ * AZ_TREE_CUT, and nothing below it is exported.  min_visits = 0, max_depth = -1 is the whole tree;
+ * max_depth = 0 the roots alone with every edge (the reference's root policy / visits / scores / moves).
+ * nodes == NULL && edges == NULL fills node_off / edge_off only, for sizing (states is then ignored).
+ * Refused with an error, nothing written to any output: a slot outside 0 .. cfg.games - 1, n < 0,
+ * min_visits < 0, NULL offsets, node_cap / edge_cap smaller than needed, one of nodes / edges NULL but not
+ * the other.
+ * May be called wherever az_search_read_roots may, mid-move after az_selfplay_run_sims included: the tree
+ * is the tree after the simulations run so far, every one backed up and none counted twice, in every form of
+ * the search (both step forms, the persistent kernel, leaves > 1, tree reuse).  Reading changes nothing.
+ * An inactive game exports what its arena holds: the tree it had when it went inactive.  The first call
+ * allocates the device scratch (12 B per node slot of the arena); a handle that never reads a tree pays
+ * nothing. */
+int az_search_read_tree(az_search* s, const int32_t* games, int n, int min_visits, int max_depth,
+                        int64_t* node_off, int64_t* edge_off,
+                        az_tree_node* nodes, int64_t node_cap,
+                        az_tree_edge* edges, int64_t edge_cap, az_pos* states);
+/* The principal variation of every slot: moves[g * cap .. g * cap + len[g]).  From the root it takes the
+ * most visited edge, ties to the larger move index (max_by's last maximum, the rule of self-play's move
+ * choice, training.rs:310-317), and descends while that edge has a child node; the last move may sit on an
+ * unexpanded or game-ending edge.  It stops before an edge with 0 visits, and at cap.  q[g]: the first
+ * move's score / visits in f32 (0 for an empty PV); visits[g]: the first move's visits.  len, q, visits may
+ * each be NULL; moves may be NULL only with cap = 0.  Callable wherever az_search_read_tree is. */
+int az_search_read_pv(az_search* s, int32_t* moves, int cap, int32_t* len, float* q, uint32_t* visits);
+
 /* traverse_new(action, apply_noise) for every game (tree.rs:239-256) after playing the
  * action on its GameState (training.rs:323-325).  result[g] receives the play_move result:
  *   AZ_ONGOING: the game goes on.  Its root is now the action's child: the child's priors are kept,
