@@ -237,6 +237,8 @@ SIGNATURES = [
     ("az_trainer_time_exchanges", C.c_int, [C.c_void_p, C.c_int]),
     ("az_rules_probe", C.c_int, [C.c_int, P(AzPos), P(C.c_int32), C.c_int, P(AzPos), P(C.c_int32), P(C.c_int32),
                                  P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_uint64), P(C.c_float)]),
+    ("az_noise_probe", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float), P(C.c_uint64), P(C.c_float),
+                                 P(C.c_int32)]),
     ("az_mx8_quantize", C.c_int, [P(C.c_float), C.c_size_t, P(C.c_uint8), P(C.c_uint8)]),
     ("az_mx8_conv_probe", C.c_int, [C.c_int, C.c_int, C.c_int, P(C.c_uint8), P(C.c_uint8), P(C.c_uint8), P(C.c_uint8),
                                     P(C.c_uint16), P(C.c_float), P(C.c_float), P(C.c_uint16), P(C.c_uint8),

@@ -195,8 +195,30 @@ def rules_probe(parents, actions, device=0):
                 fen_key=fk, planes=planes)
 
 
-DEVICE_HOST = -1                     # AZ_DEVICE_HOST: the host path of az_minimax_scores
+DEVICE_HOST = -1                     # AZ_DEVICE_HOST: the host path of az_minimax_scores / az_noise_probe
 MINIMAX_MAX_DEPTH = 8
+
+NOISE_OPS = {"logf": 0, "expf": 1, "uniform01": 2, "open01": 3, "normal": 4, "gamma": 5, "dirichlet": 6}
+
+
+def noise_probe(op, x=None, keys=None, m=1, device=0, with_fallback=False):
+    """az_noise_probe (test hook): one op of the search's random streams (csrc/detmath.h) over arrays, in a
+    kernel on GPU `device` or, with device=DEVICE_HOST, as the host compiles the same functions.
+    op: "logf" / "expf" (x: float32 arguments), "uniform01" / "open01" (keys: uint64 stream keys; the first
+    m draws of each, [n,m]), "normal" (keys), "gamma" (x: shapes, keys), "dirichlet" (x: alphas, keys; rows
+    of m components, [n,m]; with_fallback=True also returns which rows took the log-domain fallback).
+    Returns a float32 array."""
+    code = NOISE_OPS[op]
+    xa = None if x is None else np.ascontiguousarray(x, np.float32)
+    ka = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+    n = len(xa) if xa is not None else len(ka)
+    assert xa is None or ka is None or len(xa) == len(ka)
+    wide = op in ("uniform01", "open01", "dirichlet")
+    out = np.zeros((n, int(m)) if wide else n, np.float32)
+    fb = np.zeros(n, np.int32)
+    L.check(L.lib.az_noise_probe(int(device), code, n, int(m), L.fptr(xa) if xa is not None else None,
+                                 L.u64ptr(ka) if ka is not None else None, L.fptr(out), L.i32ptr(fb)))
+    return (out, fb.astype(bool)) if with_fallback else out
 
 
 def minimax_scores(positions, depth, device=0):

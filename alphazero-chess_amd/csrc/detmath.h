@@ -7,7 +7,8 @@
 // algorithms written in plain IEEE operations (compiled with -ffp-contract=off), so the
 // GPU's noise is identical bit for bit on every run and checkable.
 // Gamma(shape<1) = GammaLargeShape(shape+1) * U^(1/shape); large shape by the
-// Marsaglia-Tsang squeeze (rand_distr 0.4.3); Dirichlet x_i = g_i * (1/sum g).
+// Marsaglia-Tsang squeeze (rand_distr 0.4.3); Dirichlet x_i = g_i * (1/sum g), except for a
+// row whose draws all underflow (dirichlet_degenerate, below).
 #pragma once
 #include "chess.h"
 
@@ -139,5 +140,92 @@ AZ_HD float gamma_sample(float shape, uint64_t key) {
 AZ_HD uint64_t dirichlet_component_key(uint64_t key, int i) {
     return splitmix64(key + (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ULL);
 }
+
+// ---- the Dirichlet row: x_i = g_i * (1 / sum g), g_i = gamma_sample(alpha, component key i), the sum a
+// serial f32 sum in index order.  At a tiny alpha every g_i can underflow to 0 through u^(1/alpha) (or the
+// sum can be so small that 1/sum overflows): rand_distr yields a NaN row there.  Such a row is computed in
+// the log domain instead, from the same draws -- a stated departure from rand_distr.  A row
+// whose 1/sum is finite keeps the arithmetic above unchanged; shape >= 1 cannot degenerate and has no
+// fallback.
+AZ_HD bool dirichlet_degenerate(float alpha, float sum, float inv) {
+    return alpha < 1.0f && (sum == 0.0f || !(inv <= 3.402823466e+38f));
+}
+// log of gamma_sample's value for shape < 1, before the product underflows: log G + log(u) / shape, from
+// the same draws u (open01) and G (gamma_large(shape + 1))
+AZ_HD float gamma_small_log(float shape, uint64_t key) {
+    uint64_t ctr = 0;
+    float inv_shape = 1.0f / shape;
+    float u = open01(key, ctr);
+    float g = gamma_large(shape + 1.0f, key, ctr);
+    return det_logf(g) + det_logf(u) * inv_shape;
+}
+// the serial f32 sum of g[0..n) in index order
+AZ_HD float dirichlet_sum(const float* g, int n) {
+    float sum = 0.0f;
+    for (int k = 0; k < n; k++) sum = sum + g[k];
+    return sum;
+}
+// the largest of l[0..n).  The degenerate row: l_k = gamma_small_log, e_k = det_expf(l_k - max l),
+// x_k = e_k / sum e (serial sum)
+AZ_HD float dirichlet_log_max(const float* l, int n) {
+    float m = l[0];
+    for (int k = 1; k < n; k++) if (l[k] > m) m = l[k];
+    return m;
+}
+
+// The whole row on one thread (the host flavour of az_noise_probe); returns 1 if the row took the fallback.
+AZ_HD int dirichlet_row_serial(float alpha, int n, uint64_t key, float* x) {
+    for (int k = 0; k < n; k++) x[k] = gamma_sample(alpha, dirichlet_component_key(key, k));
+    float sum = dirichlet_sum(x, n);
+    const float inv = 1.0f / sum;
+    if (!dirichlet_degenerate(alpha, sum, inv)) {
+        for (int k = 0; k < n; k++) x[k] = x[k] * inv;
+        return 0;
+    }
+    for (int k = 0; k < n; k++) x[k] = gamma_small_log(alpha, dirichlet_component_key(key, k));
+    const float m = dirichlet_log_max(x, n);
+    for (int k = 0; k < n; k++) x[k] = det_expf(x[k] - m);
+    sum = dirichlet_sum(x, n);
+    for (int k = 0; k < n; k++) x[k] = x[k] / sum;
+    return 1;
+}
+
+#if defined(__HIPCC__)
+// The same row by one 64-thread block, as the search's root noise draws it: the lanes draw the components
+// with stride 64, lane 0 sums.  x: n floats and sh: 2 floats of shared memory; every thread of the block
+// calls it; on return x[0..n) holds the row and is visible to the block.  Returns 1 if it took the fallback.
+__device__ inline int dirichlet_row_block(float alpha, int n, uint64_t key, float* x, float* sh) {
+    const int lane = threadIdx.x;
+    for (int k = lane; k < n; k += 64) x[k] = gamma_sample(alpha, dirichlet_component_key(key, k));
+    __syncthreads();
+    if (lane == 0) {
+        const float sum = dirichlet_sum(x, n), inv = 1.0f / sum;
+        sh[0] = inv;
+        sh[1] = dirichlet_degenerate(alpha, sum, inv) ? 1.0f : 0.0f;
+    }
+    __syncthreads();
+    const float inv = sh[0];
+    const bool degenerate = sh[1] != 0.0f;
+    __syncthreads();                         // sh is written again below
+    if (!degenerate) {
+        for (int k = lane; k < n; k += 64) x[k] = x[k] * inv;
+        __syncthreads();
+        return 0;
+    }
+    for (int k = lane; k < n; k += 64) x[k] = gamma_small_log(alpha, dirichlet_component_key(key, k));
+    __syncthreads();
+    if (lane == 0) sh[0] = dirichlet_log_max(x, n);
+    __syncthreads();
+    const float m = sh[0];
+    for (int k = lane; k < n; k += 64) x[k] = det_expf(x[k] - m);
+    __syncthreads();
+    if (lane == 0) sh[1] = dirichlet_sum(x, n);
+    __syncthreads();
+    const float sum = sh[1];
+    for (int k = lane; k < n; k += 64) x[k] = x[k] / sum;
+    __syncthreads();
+    return 1;
+}
+#endif
 
 }  // namespace azc

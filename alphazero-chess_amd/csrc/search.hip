@@ -259,20 +259,12 @@ __device__ void root_noise(const Engine& E, int g, int gid, int ply, float* gam,
     const int ns = kpos[n];                 // len(moves) including under-promotion duplicates
     if (ns < 2) return;
     const uint64_t key = azc::stream_key(E.seed, (uint64_t)gid, (uint64_t)ply, 0);
-    for (int k = lane; k < ns; k += 64) gam[k] = azc::gamma_sample(E.dir_alpha, azc::dirichlet_component_key(key, k));
-    __syncthreads();
-    if (lane == 0) {
-        float sum = 0.0f;
-        for (int k = 0; k < ns; k++) sum = sum + gam[k];
-        sh[0] = 1.0f / sum;
-    }
-    __syncthreads();
-    const float inv = sh[0];
+    azc::dirichlet_row_block(E.dir_alpha, ns, key, gam, sh);   // the row eta, the one az_noise_probe reads
     const float keep = 1.0f - E.dir_eps;
     for (int e = lane; e < n; e += 64) {
         float P = edges[e].P * keep;
         const int dup = (edges[e].idx & azc::PROMO_FLAG) ? 4 : 1;
-        for (int j = 0; j < dup; j++) P = P + E.dir_eps * (gam[kpos[e] + j] * inv);
+        for (int j = 0; j < dup; j++) P = P + E.dir_eps * gam[kpos[e] + j];
         edges[e].P = P;
     }
     __syncthreads();

@@ -182,7 +182,11 @@ typedef struct {
     int games;          /* concurrent games G on this GPU (NUM_EPISODES, parameters.rs:13) */
     int sims;           /* simulations per move (NUM_SIMULATIONS, parameters.rs:32) */
     float c_puct;       /* parameters.rs:34 */
-    float dir_alpha;    /* parameters.rs:28 */
+    float dir_alpha;    /* parameters.rs:28.  A row of gamma draws whose f32 sum is 0, or so small that 1/sum
+                         * is not finite (dir_alpha < 1 only: every draw underflows through u^(1/alpha), as
+                         * 1 in 200 two-move roots do at 0.03), is normalised in the log domain from the same
+                         * draws and is a finite distribution; rand_distr yields a NaN row there.  Every other
+                         * row is g_i * (1/sum g) as in rand_distr */
     float dir_eps;      /* parameters.rs:29 */
     int temp_moves;     /* TEMPERATURE_ANNEALING, parameters.rs:31 */
     int noise;          /* Dirichlet noise at roots (training.rs:358, tree.rs:243) */
@@ -657,6 +661,24 @@ int az_wino16_pack_rows(const float* folded, int filters, uint16_t* out, size_t 
 int az_mx8_conv_probe(int device, int filters, int n, const uint8_t* act_codes, const uint8_t* act_scales,
                       const uint8_t* w_codes, const uint8_t* w_scales, const uint16_t* residual, const float* bias,
                       float* acc, uint16_t* out_bf16, uint8_t* out_codes, uint8_t* out_scales);
+
+/* ---- test hook: the random streams' device functions (the engine never calls az_noise_probe) ----
+ * One op over n items, with exactly the functions the root noise runs (csrc/detmath.h).  device >= 0: in a
+ * kernel; AZ_DEVICE_HOST (below): the same functions as the host compiles them, no GPU needed.
+ *   AZ_NOISE_LOGF / AZ_NOISE_EXPF   out[i] = det_logf(x[i]) / det_expf(x[i]), any f32 bit pattern
+ *   AZ_NOISE_UNIFORM01 / _OPEN01    out[i][0..m) = the first m draws of the stream key[i] (m in 1..4096)
+ *   AZ_NOISE_NORMAL                 out[i] = the first std_normal of the stream key[i]
+ *   AZ_NOISE_GAMMA                  out[i] = gamma_sample(shape x[i], key[i])
+ *   AZ_NOISE_DIRICHLET              out[i][0..m) = the Dirichlet row (alpha x[i], m components in
+ *                                   1..AZ_MAX_MOVES, key[i]) as one game's root noise draws it, the
+ *                                   tiny-alpha log-domain rows included (dir_alpha, above); fallback[i]
+ *                                   (may be NULL) = 1 where the row was computed that way
+ * x and key may be NULL where the op does not read them; m is ignored by the one-output ops; a shape or alpha
+ * outside (0, 1e6] is an error, as are more than 2^28 outputs; a refused call writes nothing. */
+enum { AZ_NOISE_LOGF = 0, AZ_NOISE_EXPF = 1, AZ_NOISE_UNIFORM01 = 2, AZ_NOISE_OPEN01 = 3, AZ_NOISE_NORMAL = 4,
+       AZ_NOISE_GAMMA = 5, AZ_NOISE_DIRICHLET = 6 };
+int az_noise_probe(int device, int op, int n, int m, const float* x, const uint64_t* key, float* out,
+                   int32_t* fallback);
 
 /* ---- arena opponent: the MiniMax(n) bot, chess.rs:248-322 ---------------------------------- */
 #define AZ_DEVICE_HOST (-1)

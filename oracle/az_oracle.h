@@ -94,6 +94,10 @@ float ref_det_logf(float x);
 float ref_det_expf(float x);
 float ref_gamma(float shape, uint64_t key);               /* rand_distr 0.4.3 Gamma(shape,1) */
 void  ref_dirichlet(float alpha, int n, uint64_t key, float* out); /* rand_distr Dirichlet */
+float ref_std_normal(uint64_t key, uint64_t* ctr);        /* Marsaglia polar */
+uint64_t ref_dirichlet_component_key(uint64_t key, int i);
+int   ref_dirichlet_row(float alpha, int n, uint64_t key, float* out); /* ref_dirichlet; 1 = log-domain row */
+void  ref_noise_batch(int op, int64_t n, int m, const float* x, const uint64_t* key, float* out, int32_t* fallback);
 
 /* ---- network (agent.rs) fp32, BN applied as in burn inference mode ---- */
 size_t ref_net_num_params(int blocks, int filters);

@@ -122,7 +122,7 @@ float ref_det_expf(float x) {
     return y * twopk * 0x1p-100f;
 }
 
-static float std_normal(uint64_t key, uint64_t* ctr) {   /* Marsaglia polar */
+float ref_std_normal(uint64_t key, uint64_t* ctr) {      /* Marsaglia polar */
     for (;;) {
         float u = 2.0f * ref_uniform01(key, ctr) - 1.0f;
         float v = 2.0f * ref_uniform01(key, ctr) - 1.0f;
@@ -136,7 +136,7 @@ static float gamma_large(float shape, uint64_t key, uint64_t* ctr) {
     float d = shape - 1.0f / 3.0f;
     float c = 1.0f / sqrtf(9.0f * d);
     for (;;) {
-        float x = std_normal(key, ctr);
+        float x = ref_std_normal(key, ctr);
         float v_cbrt = 1.0f + c * x;
         if (v_cbrt <= 0.0f) continue;
         float v = v_cbrt * v_cbrt * v_cbrt;
@@ -159,12 +159,70 @@ float ref_gamma(float shape, uint64_t key) {
     return gamma_large(shape, key, &ctr);
 }
 
-void ref_dirichlet(float alpha, int n, uint64_t key, float* out) {
+uint64_t ref_dirichlet_component_key(uint64_t key, int i) {
+    return ref_splitmix64(key + (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ULL);
+}
+
+/* log of ref_gamma's value for shape < 1 from the same draws: log G + log(u) / shape */
+static float gamma_small_log(float shape, uint64_t key) {
+    uint64_t ctr = 0;
+    float inv_shape = 1.0f / shape;
+    float u = ref_open01(key, &ctr);
+    float g = gamma_large(shape + 1.0f, key, &ctr);
+    return ref_det_logf(g) + ref_det_logf(u) * inv_shape;
+}
+
+/* rand_distr Dirichlet: x_i = g_i * (1 / sum g).  Departure from rand_distr: where every
+ * g_i of a row underflowed (alpha < 1: the sum is 0, or 1/sum is not finite) rand_distr yields NaN; that
+ * row is normalised in the log domain instead, from the same draws.  Returns 1 for such a row. */
+int ref_dirichlet_row(float alpha, int n, uint64_t key, float* out) {
     float sum = 0.0f;
     for (int i = 0; i < n; i++) {
-        out[i] = ref_gamma(alpha, ref_splitmix64(key + (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ULL));
+        out[i] = ref_gamma(alpha, ref_dirichlet_component_key(key, i));
         sum = sum + out[i];
     }
     float invacc = 1.0f / sum;
-    for (int i = 0; i < n; i++) out[i] = out[i] * invacc;
+    if (!(alpha < 1.0f && (sum == 0.0f || isinf(invacc)))) {
+        for (int i = 0; i < n; i++) out[i] = out[i] * invacc;
+        return 0;
+    }
+    float top = 0.0f;
+    for (int i = 0; i < n; i++) {
+        out[i] = gamma_small_log(alpha, ref_dirichlet_component_key(key, i));
+        if (i == 0 || out[i] > top) top = out[i];
+    }
+    float esum = 0.0f;
+    for (int i = 0; i < n; i++) {
+        out[i] = ref_det_expf(out[i] - top);
+        esum = esum + out[i];
+    }
+    for (int i = 0; i < n; i++) out[i] = out[i] / esum;
+    return 1;
+}
+
+void ref_dirichlet(float alpha, int n, uint64_t key, float* out) { (void)ref_dirichlet_row(alpha, n, key, out); }
+
+/* The stream functions over arrays (the tests' sweeps): op 0 det_logf(x[i]), 1 det_expf(x[i]), 2 / 3 the
+ * first m uniform01 / open01 draws of key[i], 4 the first std_normal of key[i], 5 gamma(x[i], key[i]),
+ * 6 the Dirichlet row (x[i], m, key[i]) with fallback[i] (may be NULL) = ref_dirichlet_row's return,
+ * 7 the log-domain gamma (x[i] < 1, key[i]) the degenerate rows are built from. */
+void ref_noise_batch(int op, int64_t n, int m, const float* x, const uint64_t* key, float* out, int32_t* fallback) {
+    for (int64_t i = 0; i < n; i++) {
+        uint64_t ctr = 0;
+        switch (op) {
+        case 0: out[i] = ref_det_logf(x[i]); break;
+        case 1: out[i] = ref_det_expf(x[i]); break;
+        case 2: for (int j = 0; j < m; j++) out[i * m + j] = ref_uniform01(key[i], &ctr); break;
+        case 3: for (int j = 0; j < m; j++) out[i * m + j] = ref_open01(key[i], &ctr); break;
+        case 4: out[i] = ref_std_normal(key[i], &ctr); break;
+        case 5: out[i] = ref_gamma(x[i], key[i]); break;
+        case 6: {
+            int fb = ref_dirichlet_row(x[i], m, key[i], out + i * m);
+            if (fallback) fallback[i] = fb;
+            break;
+        }
+        case 7: out[i] = gamma_small_log(x[i], key[i]); break;
+        default: break;
+        }
+    }
 }

@@ -93,6 +93,18 @@ def lib():
         L.ref_gamma.argtypes = [C.c_float, C.c_uint64]
         L.ref_gamma.restype = C.c_float
         L.ref_dirichlet.argtypes = [C.c_float, C.c_int, C.c_uint64, P(C.c_float)]
+        L.ref_uniform01.argtypes = [C.c_uint64, P(C.c_uint64)]
+        L.ref_uniform01.restype = C.c_float
+        L.ref_open01.argtypes = [C.c_uint64, P(C.c_uint64)]
+        L.ref_open01.restype = C.c_float
+        L.ref_std_normal.argtypes = [C.c_uint64, P(C.c_uint64)]
+        L.ref_std_normal.restype = C.c_float
+        L.ref_dirichlet_component_key.argtypes = [C.c_uint64, C.c_int]
+        L.ref_dirichlet_component_key.restype = C.c_uint64
+        L.ref_dirichlet_row.argtypes = [C.c_float, C.c_int, C.c_uint64, P(C.c_float)]
+        L.ref_noise_batch.argtypes = [C.c_int, C.c_int64, C.c_int, P(C.c_float), P(C.c_uint64), P(C.c_float),
+                                      P(C.c_int32)]
+        L.ref_noise_batch.restype = None
         L.ref_net_num_params.argtypes = [C.c_int, C.c_int]
         L.ref_net_num_params.restype = C.c_size_t
         L.ref_net_create.argtypes = [C.c_int, C.c_int, P(C.c_float)]
@@ -274,6 +286,31 @@ def dirichlet(alpha, n, key):
     out = np.zeros(n, np.float32)
     lib().ref_dirichlet(alpha, n, key, _fp(out))
     return out
+
+
+NOISE_OPS = {"logf": 0, "expf": 1, "uniform01": 2, "open01": 3, "normal": 4, "gamma": 5, "dirichlet": 6,
+             "gamma_log": 7}
+
+
+def noise_batch(op, x=None, keys=None, m=1, with_fallback=False):
+    """ref_noise_batch: one stream function over arrays.  "logf" / "expf" (x), "uniform01" / "open01" (keys; the
+    first m draws of each, [n,m]), "normal" (keys), "gamma" (x: shapes, keys), "dirichlet" (x: alphas, keys;
+    rows of m components, [n,m]; with_fallback=True also returns which rows were normalised in the log
+    domain), "gamma_log" (x: shapes < 1, keys: the log of the gamma draw those rows are built from)."""
+    xa = None if x is None else np.ascontiguousarray(x, np.float32)
+    ka = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+    n = len(xa) if xa is not None else len(ka)
+    assert xa is None or ka is None or len(xa) == len(ka)
+    out = np.zeros((n, int(m)) if op in ("uniform01", "open01", "dirichlet") else n, np.float32)
+    fb = np.zeros(n, np.int32)
+    lib().ref_noise_batch(NOISE_OPS[op], n, int(m), _fp(xa) if xa is not None else None,
+                          _u64p(ka) if ka is not None else None, _fp(out), _i32p(fb))
+    return (out, fb.astype(bool)) if with_fallback else out
+
+
+def component_keys(key, n):
+    """the stream keys of a Dirichlet row's n gamma draws"""
+    return np.array([lib().ref_dirichlet_component_key(int(key), i) for i in range(n)], np.uint64)
 
 
 # ------------------------------------------------------------------ network
